@@ -19,8 +19,26 @@ rank 0's JSON line; under torch.distributed.run it is one of the ranks.
 Next to the headline, in the same JSON line:
   roofline      algorithmic bytes per launch / mean kernel time per launch (HIP
                 events on the launch stream, strom_perfmon.time_kern_exec_ns),
-                against the nominal 8 TB/s and against the box's own
-                streaming-read rate (strom_membw_probe)
+                against the nominal 8 TB/s (with --full also against the box's
+                own streaming-read rate, strom_membw_probe)
+
+A plain run does only what the headline needs: table set-up, --warmup steps,
+--steps timed steps, the outputs if --dump-outputs is given, the line.
+`--dump-outputs DIR` writes what the timed path computed in its last step, as
+float32 / float64 .npy files (inputs are seeded: two builds compare file by file):
+  nitems, errcode          per chunk, what strom_task_wait hands the caller
+  selected_rowid_sum       per chunk, the sum of the 0-based ids of the rows
+                           results[] holds (qual true or CpuReCheck)
+  sample_rows, selected_sample
+                           a fixed seeded sample of the table's rows and, for
+                           each, 1 (qual true), -1 (CpuReCheck) or 0
+The row ids stay in HBM in the timed path (STROM_RESULTS_ON_DEVICE) and are
+released when the request is waited for; the last three files come from one
+more untimed pass of the same program over the same chunks with results copied
+back, whose per-chunk counts and errcodes are checked against the last timed
+step's.
+
+`--full` adds, after the headline, everything else the bench measures:
   cpu_baseline  the CPU oracle (oracle/, a port: tuple-at-a-time over ROW
                 format heap pages, expression tree interpreted per row -- the
                 shape of PostgreSQL's SeqScan + ExecQual), bounded sample
@@ -782,6 +800,40 @@ def sharded_gpupreagg(args, rank, world, local_rank, barrier, dist, torch, measu
     return out
 
 
+DUMP_SAMPLE_ROWS = 1 << 21       # rows of the table in the seeded sample of --dump-outputs
+DUMP_SAMPLE_SEED = 0x5eed0d0d
+
+
+def dump_outputs(outdir, rank, scan, chunks, last_step):
+    """--dump-outputs: the headline's answers of the last timed step (see the module docstring).
+    A rank other than 0 writes <name>_rank<r>.npy.  At most ~25 MB in all, whatever --rows."""
+    assert len(last_step) == len(chunks), "last timed step: %d answers for %d chunks" % (len(last_step), len(chunks))
+    offsets = np.cumsum([0] + [ds.nitems for ds in chunks])
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, offsets[-1], min(DUMP_SAMPLE_ROWS, offsets[-1])))
+    sample = np.zeros(len(rows), dtype=np.float32)
+    idsum = np.zeros(len(chunks), dtype=np.float64)
+    for i, ds in enumerate(chunks):
+        res = scan.scan_chunk(ds)                   # results[] copied back this time
+        assert (res.nitems, res.errcode) == last_step[i], \
+            "chunk %d: untimed pass (%d, %d) vs last timed step %s" % (i, res.nitems, res.errcode, last_step[i])
+        r = res.results.astype(np.int64)
+        idsum[i] = float(np.abs(r).sum() - len(r))   # 0-based ids of the rows returned
+        flags = np.zeros(ds.nitems, dtype=np.int8)
+        flags[r[r > 0] - 1] = 1
+        flags[-r[r < 0] - 1] = -1
+        lo, hi = np.searchsorted(rows, [offsets[i], offsets[i + 1]])
+        sample[lo:hi] = flags[rows[lo:hi] - offsets[i]]
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    arrays = {"nitems": np.array([n for n, _ in last_step], dtype=np.float64),
+              "errcode": np.array([e for _, e in last_step], dtype=np.float64),
+              "selected_rowid_sum": idsum,
+              "sample_rows": rows.astype(np.float64),
+              "selected_sample": sample}
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), arr)
+
+
 def claim_stdout():
     """stdout carries exactly ONE JSON line, but RCCL prints a version banner on the C stdout
     when a communicator is made (whenever that happens: at init, at the first collective).
@@ -849,15 +901,22 @@ def main():
     ap.add_argument("--window", type=int, default=2,
                     help="requests kept in flight (pg_strom.max_async_chunks)")
     ap.add_argument("--selectivity", type=float, default=0.10)
-    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="budget of each CPU baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the box's streaming-read peak, the CPU baselines, the sharded GpuPreAgg "
+                         "region and (N=1) the other operators; a plain run times the headline only")
+    ap.add_argument("--cpu-seconds", type=float, default=5.0, help="budget of each CPU baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the GpuHashJoin / GpuPreAgg / chain figures reported next to the headline")
-    ap.add_argument("--no-sharded", action="store_true", help="skip the sharded GpuPreAgg + RCCL merge region")
+                    help="--full without the GpuHashJoin / GpuPreAgg / chain figures reported next to the headline")
+    ap.add_argument("--no-sharded", action="store_true", help="--full without the sharded GpuPreAgg + RCCL merge region")
     ap.add_argument("--sharded-timeout", type=int, default=240,
                     help="seconds the sharded GpuPreAgg region may take before the headline is printed without it")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_worker:
         kind, kk, cc, secs = args.cpu_worker.split(",")
         cpu_worker(kind, np.int32(int(kk)), float(cc), float(secs))
@@ -916,6 +975,7 @@ def main():
 
     kern_ns = []
     nitems_seen = []
+    last_step = []                              # (nitems, errcode) per chunk of the last timed step
 
     import collections
 
@@ -933,6 +993,8 @@ def main():
             if record:
                 kern_ns.append(res.perfmon["time_kern_exec_ns"])
                 nitems_seen.append(res.nitems)
+                if step == nsteps - 1:
+                    last_step.append((res.nitems, res.errcode))
 
         for step in range(nsteps):
             for ds in chunks:
@@ -961,10 +1023,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        log("writing the outputs of the last timed step")
+        dump_outputs(args.dump_outputs, rank, scan, chunks, last_step)
+
     # the box's own streaming-read rate: the "measured peak" denominator
     measured_peak = None
     gbs = ctypes.c_double(0.0)
-    if lib.strom_membw_probe(0, 1_200_000_000, 10, ctypes.byref(gbs)) == 0 and gbs.value > 0:
+    if args.full and lib.strom_membw_probe(0, 1_200_000_000, 10, ctypes.byref(gbs)) == 0 and gbs.value > 0:
         measured_peak = gbs.value
 
     scan.end()
@@ -973,7 +1039,7 @@ def main():
     nchunks = len(chunks)
     del chunks
 
-    with_cpu = (ngpus == 1 and not args.no_cpu_baseline)
+    with_cpu = (args.full and ngpus == 1 and not args.no_cpu_baseline)
 
     def cpu_blocks(kind):
         if not with_cpu:
@@ -1034,7 +1100,7 @@ def main():
                 out.update(extra)
             print(json.dumps(out), file=line_out, flush=True)
 
-    if not args.no_sharded:
+    if args.full and not args.no_sharded:
         # second region: every rank takes part (RCCL).  A rank that does not come back from
         # it within the limit must not take the headline with it: the watchdog prints the
         # line (with the failure named) and ends the process.
@@ -1062,7 +1128,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline("scan", k, c, 2 * args.cpu_seconds)
             out["cpu_baseline_all_cores"] = cpu_baseline_all_cores("scan", k, c, args.cpu_seconds)
             out["cpu_baseline_columnar"] = cpu_baseline_columnar(k, c)
-        if ngpus == 1 and not args.no_extras:
+        if args.full and ngpus == 1 and not args.no_extras:
             try:
                 log("other operators")
                 out["operators"] = operator_figures(args, k, c, measured_peak, cpu_blocks)

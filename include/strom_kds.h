@@ -293,6 +293,32 @@ typedef struct {
 #define KERN_GPUSCAN_DMASEND_LENGTH(kgs)	\
 	(KERN_GPUSCAN_PARAMBUF_LENGTH(kgs) + offsetof(kern_resultbuf, results))
 
+/*
+ * resident COLUMN chunk, no row map (gpuscan_qual_column_resident): the
+ * request travels as the kernel argument and the kernel publishes its own
+ * result head, so that no copy sits between two consecutive scans.
+ *   slot       per-request cursor (low 32 bits: entries reserved, high: work-
+ *              groups finished) and error word, zero on entry; the last
+ *              work-group leaves it zero again
+ *   host_slot  pinned host words {nitems, errcode} the last work-group writes
+ */
+#define KERN_GPUSCAN_KARG_PARAMBUF		512		/* larger parambufs take the copied path */
+typedef struct {
+	cl_ulong	cursor;
+	cl_int		errcode;
+	cl_uint		__padding__[29];	/* one 128-byte line per slot */
+} kern_gpuscan_slot;
+
+typedef struct {
+	const kern_data_store *kds;
+	kern_resultbuf *kresults;		/* device result buffer: results[] and the head published */
+	kern_gpuscan_slot *slot;
+	cl_uint	   *host_slot;
+	cl_uint		res_head[5];		/* nrels, nrooms, nitems, errcode, flag bytes of the host image */
+	cl_uint		__padding__;
+	cl_ulong	kparams[KERN_GPUSCAN_KARG_PARAMBUF / sizeof(cl_ulong)];	/* kern_parambuf image */
+} kern_gpuscan_column_args;
+
 /* ----------------------------------------------------------------
  * hash join: chained table that owns whole inner heap tuples
  * ---------------------------------------------------------------- */

@@ -27,6 +27,11 @@
  *       per 1e8-row chunk instead of one per work-group per 256 rows --
  *       and the flush itself is a contiguous coalesced store.
  *
+ *   gpuscan_qual_column_resident  the same walk over a resident chunk: the
+ *       request is the kernel argument, the cursor and the error word live
+ *       in a ring slot, and the kernel publishes its result head itself
+ *       (strom_kds.h: kern_gpuscan_column_args).
+ *
  *   gpuscan_qual_generic  any format, optional kern_row_map.  Same
  *       compaction, rows fetched one datum at a time through kern_get_datum
  *       (this is the heap-tuple walk the reference does for every row).
@@ -110,9 +115,31 @@ typedef gpuscan_stage_t<GPUSCAN_STAGE> gpuscan_stage;
 #endif
 typedef gpuscan_stage_t<GPUSCAN_GENERIC_STAGE> gpuscan_generic_stage;
 
-template <typename STAGE>
+/*
+ * One entry of results[]: written once and read elsewhere.  GPUSCAN_STORE_NT=1
+ * (default): non-temporal stores keep them out of the L2 write-allocate path
+ * of the read stream (+5 % at 10 % selectivity, +8 % at 49 %:
+ * profiles/r01_gpuscan_tune_v2.txt).  0: plain stores.  2: write-through
+ * (agent-scope relaxed atomic stores, sc1), which leave no dirty line for the
+ * end of the kernel to write back.
+ */
 STROM_DEVICE void
-gpuscan_stage_flush(STAGE &stage, kern_resultbuf *kresults, cl_uint fill)
+gpuscan_store_result(cl_int *p, cl_int v)
+{
+#if !defined(GPUSCAN_STORE_NT) || GPUSCAN_STORE_NT == 1
+	__builtin_nontemporal_store(v, p);
+#elif GPUSCAN_STORE_NT == 2
+	__hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+	*p = v;
+#endif
+}
+
+/* 'cursor' counts the entries of results[] (kern_resultbuf.nitems, or the low
+ * half of the resident kernel's ring slot word) */
+template <typename STAGE, typename CURSOR>
+STROM_DEVICE void
+gpuscan_stage_flush(STAGE &stage, CURSOR *cursor, cl_int *results, cl_uint nrooms, cl_uint fill)
 {
 	/* caller guarantees a barrier since the last write into the stage */
 	if (fill == 0)
@@ -123,25 +150,17 @@ gpuscan_stage_flush(STAGE &stage, kern_resultbuf *kresults, cl_uint fill)
 #if defined(GPUSCAN_ABLATE) && GPUSCAN_ABLATE == 2
 	/* diagnostic build (wrong results): no reservation atomic */
 	if (threadIdx.x == 0)
-		stage.flush_base = (blockIdx.x * 7919u) % (kresults->nrooms - GPUSCAN_STAGE);
+		stage.flush_base = (blockIdx.x * 7919u) % (nrooms - GPUSCAN_STAGE);
 #else
 	if (threadIdx.x == 0)
-		stage.flush_base = atomicAdd(&kresults->nitems, fill);
+		stage.flush_base = (cl_uint)atomicAdd(cursor, (CURSOR)fill);
 #endif
 	__syncthreads();
 	cl_uint		base = stage.flush_base;
-	cl_int	   *dest = kresults->results + base;
+	cl_int	   *dest = results + base;
 #if !defined(GPUSCAN_ABLATE) || GPUSCAN_ABLATE != 1
-#if !defined(GPUSCAN_STORE_NT) || GPUSCAN_STORE_NT
-	/* results are written once and read elsewhere: non-temporal stores keep
-	 * them out of the L2 write-allocate path of the read stream (+5 % at 10 %
-	 * selectivity, +8 % at 49 %: profiles/r01_gpuscan_tune_v2.txt) */
 	for (cl_uint i = threadIdx.x; i < fill; i += GPUSCAN_BLOCK)
-		__builtin_nontemporal_store(stage.entries[i], &dest[i]);
-#else
-	for (cl_uint i = threadIdx.x; i < fill; i += GPUSCAN_BLOCK)
-		dest[i] = stage.entries[i];
-#endif
+		gpuscan_store_result(&dest[i], stage.entries[i]);
 #else
 	/* diagnostic build (wrong results): no result stores */
 	if (fill == 0xffffffffu)
@@ -229,13 +248,15 @@ struct gpuscan_column_tile {
 	int __dummy;
 };
 
-extern "C" __global__ void
-__launch_bounds__(GPUSCAN_BLOCK)
-gpuscan_qual_column(kern_gpuscan *kgpuscan, const kern_data_store *kds)
+/* returns the entries still in the stage (a barrier has passed since they were
+ * written); the chunk's error is written back */
+template <typename CURSOR>
+STROM_DEVICE cl_uint
+gpuscan_column_body(gpuscan_stage &stage,
+					const kern_parambuf *kparams,
+					const kern_data_store *kds,
+					CURSOR *cursor, cl_int *results, cl_uint nrooms, cl_int *errword)
 {
-	__shared__ gpuscan_stage stage;
-	const kern_parambuf *kparams = KERN_GPUSCAN_PARAMBUF(kgpuscan);
-	kern_resultbuf *kresults = KERN_GPUSCAN_RESULTBUF(kgpuscan);
 	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
 	cl_uint		nitems = kds->nitems;
 	cl_uint		ntiles = (nitems + GPUSCAN_TILE_ROWS - 1) / GPUSCAN_TILE_ROWS;
@@ -310,7 +331,7 @@ gpuscan_qual_column(kern_gpuscan *kgpuscan, const kern_data_store *kds)
 		}
 		if (fill + GPUSCAN_TILE_ROWS > GPUSCAN_STAGE)
 		{
-			gpuscan_stage_flush(stage, kresults, fill);
+			gpuscan_stage_flush(stage, cursor, results, nrooms, fill);
 			fill = 0;
 		}
 #pragma unroll
@@ -336,8 +357,86 @@ gpuscan_qual_column(kern_gpuscan *kgpuscan, const kern_data_store *kds)
 		}
 		fill += gpuscan_stage_append(stage, fill, tile_base, st);
 	}
-	gpuscan_stage_flush(stage, kresults, fill);
-	kern_writeback_error_status(&kresults->errcode, chunk_error);
+	kern_writeback_error_status(errword, chunk_error);
+	return fill;
+}
+
+/* the request head in device memory (host chunks, the copied path) */
+extern "C" __global__ void
+__launch_bounds__(GPUSCAN_BLOCK)
+gpuscan_qual_column(kern_gpuscan *kgpuscan, const kern_data_store *kds)
+{
+	__shared__ gpuscan_stage stage;
+	kern_resultbuf *kresults = KERN_GPUSCAN_RESULTBUF(kgpuscan);
+
+	cl_uint		fill = gpuscan_column_body(stage, KERN_GPUSCAN_PARAMBUF(kgpuscan), kds, &kresults->nitems,
+										   kresults->results, kresults->nrooms, &kresults->errcode);
+	gpuscan_stage_flush(stage, &kresults->nitems, kresults->results, kresults->nrooms, fill);
+}
+
+/*
+ * resident chunk: the parambuf is the kernel argument, and the cursor and the
+ * error word live in a ring slot.  The slot's cursor word counts reserved
+ * entries in its low half and finished work-groups in its high half, so a
+ * work-group's last reservation is also its ticket: the one that draws the
+ * last ticket knows nitems without another atomic, publishes the result head
+ * -- into the device kern_resultbuf (row maps and chained operators read it
+ * there) and into the request's pinned host words -- and leaves the slot zero
+ * for its next request.
+ */
+extern "C" __global__ void
+__launch_bounds__(GPUSCAN_BLOCK)
+gpuscan_qual_column_resident(kern_gpuscan_column_args args)
+{
+	__shared__ gpuscan_stage stage;
+	__shared__ bool	last;
+	kern_gpuscan_slot *slot = args.slot;
+	cl_int	   *results = args.kresults->results;
+	cl_uint		fill = gpuscan_column_body(stage, (const kern_parambuf *)args.kparams, args.kds,
+										   &slot->cursor, results, args.res_head[1], &slot->errcode);
+	/*
+	 * __syncthreads() alone waits for no vector-memory counter on this chip.  So every wave
+	 * first waits until its own memory operations are acknowledged -- the error word's
+	 * compare-and-swap above all, which may be issued without a return -- and only then
+	 * meets the barrier: the work-group's error word and reservations are performed before
+	 * its ticket is drawn.  What the last work-group reads are atomics at the device's
+	 * coherence point, so no agent-scope release fence is needed (on this chip one writes
+	 * back the XCD's L2, once per work-group: measured 650 instead of 200 us per 1e8-row
+	 * chunk).  Same wait as STROM_PUBLISH_STATE (strom_common.h), same formal fallback.
+	 */
+#if STROM_FORMAL_PUBLISH
+	__threadfence();
+#else
+	__builtin_amdgcn_s_waitcnt(0x0f70);		/* vmcnt(0) in the gfx9 encoding */
+#endif
+	__syncthreads();
+	if (threadIdx.x == 0)
+	{
+		cl_ulong	old = atomicAdd(&slot->cursor, (1UL << 32) + fill);
+		stage.flush_base = (cl_uint)old;
+		last = ((cl_uint)(old >> 32) == gridDim.x - 1);
+	}
+	__syncthreads();
+	cl_int	   *dest = results + stage.flush_base;
+	for (cl_uint i = threadIdx.x; i < fill; i += GPUSCAN_BLOCK)
+		gpuscan_store_result(&dest[i], stage.entries[i]);
+	if (threadIdx.x == 0 && last)
+	{
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+		cl_uint		nitems = stage.flush_base + fill;
+		cl_int		errcode = __hip_atomic_load(&slot->errcode, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		cl_uint	   *head = (cl_uint *)args.kresults;
+
+		head[0] = args.res_head[0];			/* nrels */
+		head[1] = args.res_head[1];			/* nrooms */
+		head[2] = nitems;
+		head[3] = (cl_uint)errcode;
+		head[4] = args.res_head[4];			/* has_rechecks, all_visible */
+		__hip_atomic_store(&args.host_slot[0], nitems, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(&args.host_slot[1], (cl_uint)errcode, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		__hip_atomic_store(&slot->cursor, (cl_ulong)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(&slot->errcode, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
 }
 
 /* ====================================================================== *
@@ -382,7 +481,7 @@ gpuscan_qual_generic_body(kern_gpuscan *kgpuscan,
 
 		if (fill + GPUSCAN_TILE_ROWS > GPUSCAN_GENERIC_STAGE)
 		{
-			gpuscan_stage_flush(stage, kresults, fill);
+			gpuscan_stage_flush(stage, &kresults->nitems, kresults->results, kresults->nrooms, fill);
 			fill = 0;
 		}
 #pragma unroll
@@ -444,7 +543,7 @@ gpuscan_qual_generic_body(kern_gpuscan *kgpuscan,
 			fill += n;
 		}
 	}
-	gpuscan_stage_flush(stage, kresults, fill);
+	gpuscan_stage_flush(stage, &kresults->nitems, kresults->results, kresults->nrooms, fill);
 	kern_writeback_error_status(&kresults->errcode, chunk_error);
 }
 

@@ -43,6 +43,162 @@ struct gpuscan_request {
 		}																	\
 	} while (0)
 
+/*
+ * grid: enough persistent work-groups to fill every CU at the occupancy the
+ * kernel's registers and LDS stage allow, never more than tiles
+ * (clserv_compute_workgroup_size's job, opencl_devinfo.c:1126-1231)
+ */
+void
+gpuscan_geometry(Device *dev, hipFunction_t fn, uint32_t nrows, size_t *p_grid, int *p_block)
+{
+	int		block = 256;
+	if (const char *v = getenv("STROM_GPUSCAN_BLOCK"))
+		block = atoi(v);
+	int		quads = 1;
+	if (const char *v = getenv("STROM_GPUSCAN_QUADS"))
+		quads = atoi(v);
+	size_t	tile_rows = (size_t)block * 4 * quads;
+	size_t	ntiles = (nrows + tile_rows - 1) / tile_rows;
+	int		per_cu = 0;
+	if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess
+		|| per_cu < 1)
+		per_cu = 1;
+	if (const char *v = getenv("STROM_GPUSCAN_BLOCKS_PER_CU"))
+		per_cu = std::max(1, atoi(v));
+	size_t	grid = (size_t)dev->prop.multiProcessorCount * per_cu;
+	if (grid > ntiles)
+		grid = ntiles;
+	if (grid < 1)
+		grid = 1;
+	*p_grid = grid;
+	*p_block = block;
+}
+
+/* completer side of both paths: the result head is in kres_host; results[] follow unless they stay
+ * on the device */
+void
+gpuscan_finish_results(strom_task_impl *t, kern_resultbuf *kres_host, char *d_kgs, size_t res_offset,
+					   bool results_on_device, hipStream_t st)
+{
+	if (StromErrorIsSignificant(kres_host->errcode))
+		t->errcode = kres_host->errcode;
+	t->res_nitems = kres_host->nitems;
+	if (results_on_device || kres_host->nitems == 0)
+		return;
+	size_t	len = sizeof(cl_int) * (size_t)kres_host->nitems;
+	auto	t0 = std::chrono::steady_clock::now();
+	hipError_t rc = hipMemcpyAsync(kres_host->results,
+								   d_kgs + res_offset + offsetof(kern_resultbuf, results),
+								   len, hipMemcpyDeviceToHost, st);
+	if (rc == hipSuccess)
+		rc = hipStreamSynchronize(st);
+	if (rc != hipSuccess)
+		t->errcode = hip_errcode(rc, "recv results[]");
+	t->pfm.num_dma_recv++;
+	t->pfm.bytes_dma_recv += len;
+	t->pfm.time_dma_recv += (cl_ulong)std::chrono::duration<double, std::micro>
+		(std::chrono::steady_clock::now() - t0).count();
+}
+
+/*
+ * Resident COLUMN chunk, no row map: the kernel dispatch is the only packet
+ * the request puts on its stream.  The parambuf travels as the kernel
+ * argument (no copy of the request head), the kernel's last work-group
+ * publishes the result head into the device kern_resultbuf and into the
+ * ring slot's pinned host words (no copy back), and the kernel's own
+ * dispatch carries the begin / end events the completer waits on.
+ */
+void
+gpuscan_launch_resident(strom_task_impl *task, Program *prog, const gpuscan_request &req, int slot)
+{
+	Device	   *dev = task->dev;
+	kern_gpuscan *kgs = req.kgpuscan;
+	kern_resultbuf *kres_host = KERN_GPUSCAN_RESULTBUF(kgs);
+	size_t		res_offset = KERN_GPUSCAN_PARAMBUF_LENGTH(kgs);
+	int			errcode = 0;
+
+	/* given back once the completer has seen the request end, however it ends */
+	task->at_complete.push_back([dev, slot]() { dev->scan_slot_put(slot); });
+	hipFunction_t fn = prog->get_function(dev, "gpuscan_qual_column_resident", &errcode);
+	if (!fn)
+	{
+		task_fail(task, errcode);
+		return;
+	}
+	char	   *d_kgs = (char *)dev->pool.alloc(KERN_GPUSCAN_LENGTH(kgs));
+	if (!d_kgs)
+	{
+		task_fail(task, StromError_OutOfMemory);
+		return;
+	}
+	task->main_devptr = d_kgs;
+	task->keep_main = ((req.flags & STROM_RESULTS_ON_DEVICE) != 0);
+
+	kern_gpuscan_column_args args;
+	memset(&args, 0, sizeof(args));
+	args.kds = (const kern_data_store *)req.kds_dev->devptr;
+	args.kresults = (kern_resultbuf *)(d_kgs + res_offset);
+	args.slot = dev->scan_slots + slot;
+	volatile cl_uint *host_slot = dev->scan_slots_host + 16 * slot;
+	args.host_slot = (cl_uint *)host_slot;
+	memcpy(args.res_head, kres_host, sizeof(args.res_head));
+	memcpy(args.kparams, KERN_GPUSCAN_PARAMBUF(kgs), KERN_GPUSCAN_PARAMBUF(kgs)->length);
+	/* a head the kernel never published shows as nitems > nrooms */
+	host_slot[0] = 0xffffffffu;
+	host_slot[1] = 0;
+
+	size_t		grid;
+	int			block;
+	gpuscan_geometry(dev, fn, req.nrows, &grid, &block);
+	void	   *params[] = { &args };
+	if (use_ext_launch())
+	{
+		hipEvent_t	ev_begin = (task->pfm.enabled ? task_event_slot(task) : nullptr);	/* ev[0] */
+		hipEvent_t	ev_done = task_event_slot(task);									/* ev[1] */
+		if ((task->pfm.enabled && !ev_begin) || !ev_done)
+		{
+			task_fail(task, StromError_HipInternal);
+			return;
+		}
+		REQ_CHECK(hipExtModuleLaunchKernel(fn, (uint32_t)(grid * block), 1, 1, block, 1, 1, 0, task->stream,
+										   params, nullptr, ev_begin, ev_done, 0),
+				  "launch gpuscan kernel");
+	}
+	else
+	{
+		if (task->pfm.enabled)
+			task_event(task);									/* ev[0] */
+		REQ_CHECK(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, 0, task->stream,
+										params, nullptr),
+				  "launch gpuscan kernel");
+		task_event(task);										/* ev[1] */
+	}
+	task->pfm.num_kern_exec++;
+	task->ev_kernel_only = task->pfm.enabled;
+
+	bool		results_on_device = (req.flags & STROM_RESULTS_ON_DEVICE) != 0;
+	cl_uint		nrooms = kres_host->nrooms;
+	task->res_offset = res_offset;
+	task->res_is_scan = true;
+	task->finish = [kres_host, d_kgs, res_offset, results_on_device, host_slot, nrooms](strom_task_impl *t)
+	{
+		kres_host->nitems = host_slot[0];
+		kres_host->errcode = (cl_int)host_slot[1];
+		if (kres_host->nitems > nrooms)
+		{
+			kres_host->nitems = 0;
+			t->errcode = StromError_HipInternal;
+			return;
+		}
+		/* results[] come back on copy_out: on the scan stream the copy would sit between two
+		 * scans, and its synchronisation would wait for every scan queued behind this one.  The
+		 * kernel is over (the completer waited for its end event): no stream wait is needed. */
+		gpuscan_finish_results(t, kres_host, d_kgs, res_offset, results_on_device,
+							   t->dev->copy_out ? t->dev->copy_out : t->stream);
+	};
+	task_enqueue(task);
+}
+
 void
 gpuscan_launch(strom_task_impl *task, Program *prog, gpuscan_request req)
 {
@@ -74,6 +230,24 @@ gpuscan_launch(strom_task_impl *task, Program *prog, gpuscan_request req)
 		task->stream = dev->streams[1 + dev->next_stream++ % (dev->streams.size() - 1)];
 
 	bool		use_column = (req.format == KDS_FORMAT_COLUMN && req.krowmap == nullptr && req.rowmap_dev == nullptr);
+	/*
+	 * A text / character(n) parameter is the address of its datum inside the parambuf
+	 * (strom_textlib.h): with the parambuf as the kernel argument that would be an address
+	 * of the kernel's private copy, which the text library reads as global memory.  Such
+	 * programs keep the parambuf in device memory.
+	 */
+	static const bool	resident_path = (getenv("STROM_GPUSCAN_COPIED_HEAD") == nullptr);
+	if (resident_path && use_column && req.kds_dev && !(prog->extra_flags & DEVFUNC_NEEDS_TEXTLIB) &&
+		KERN_GPUSCAN_PARAMBUF(kgs)->length <= KERN_GPUSCAN_KARG_PARAMBUF)
+	{
+		/* more requests in flight than slots: the copied path below */
+		int		slot = dev->scan_slot_get();
+		if (slot >= 0)
+		{
+			gpuscan_launch_resident(task, prog, req, slot);
+			return;
+		}
+	}
 	hipFunction_t fn = prog->get_function(dev, use_column ? "gpuscan_qual_column"
 										  : "gpuscan_qual_generic", &errcode);
 	if (!fn)
@@ -174,31 +348,10 @@ gpuscan_launch(strom_task_impl *task, Program *prog, gpuscan_request req)
 	else
 		task_event(task);								/* ev[1] */
 
-	/*
-	 * grid: enough persistent work-groups to fill every CU at the
-	 * occupancy the kernel's LDS stage allows, never more than tiles
-	 * (clserv_compute_workgroup_size's job, opencl_devinfo.c:1126-1231)
-	 */
 	{
-		int		block = 256;
-		if (const char *v = getenv("STROM_GPUSCAN_BLOCK"))
-			block = atoi(v);
-		int		quads = 1;
-		if (const char *v = getenv("STROM_GPUSCAN_QUADS"))
-			quads = atoi(v);
-		size_t	tile_rows = (size_t)block * 4 * quads;
-		size_t	ntiles = (req.nrows + tile_rows - 1) / tile_rows;
-		int		per_cu = 0;
-		if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess
-			|| per_cu < 1)
-			per_cu = 1;
-		if (const char *v = getenv("STROM_GPUSCAN_BLOCKS_PER_CU"))
-			per_cu = std::max(1, atoi(v));
-		size_t	grid = (size_t)dev->prop.multiProcessorCount * per_cu;
-		if (grid > ntiles)
-			grid = ntiles;
-		if (grid < 1)
-			grid = 1;
+		size_t	grid;
+		int		block;
+		gpuscan_geometry(dev, fn, req.nrows, &grid, &block);
 		void   *a_kgs = d_kgs;
 		const void *a_kds = d_kds;
 		const void *a_toast = nullptr;
@@ -236,25 +389,8 @@ gpuscan_launch(strom_task_impl *task, Program *prog, gpuscan_request req)
 	{
 		if (stage_res)
 			memcpy(kres_host, stage_res, offsetof(kern_resultbuf, results));
-		if (StromErrorIsSignificant(kres_host->errcode))
-			t->errcode = kres_host->errcode;
-		t->res_nitems = kres_host->nitems;
-		if (results_on_device || kres_host->nitems == 0)
-			return;
-		size_t	len = sizeof(cl_int) * (size_t)kres_host->nitems;
-		auto	t0 = std::chrono::steady_clock::now();
-		hipStream_t	st = (t->has_ev_prep ? t->dev->copy_out : t->stream);
-		hipError_t rc = hipMemcpyAsync(kres_host->results,
-									   d_kgs + res_offset + offsetof(kern_resultbuf, results),
-									   len, hipMemcpyDeviceToHost, st);
-		if (rc == hipSuccess)
-			rc = hipStreamSynchronize(st);
-		if (rc != hipSuccess)
-			t->errcode = hip_errcode(rc, "recv results[]");
-		t->pfm.num_dma_recv++;
-		t->pfm.bytes_dma_recv += len;
-		t->pfm.time_dma_recv += (cl_ulong)std::chrono::duration<double, std::micro>
-			(std::chrono::steady_clock::now() - t0).count();
+		gpuscan_finish_results(t, kres_host, d_kgs, res_offset, results_on_device,
+							   t->has_ev_prep ? t->dev->copy_out : t->stream);
 	};
 	task_enqueue(task);
 }

@@ -93,6 +93,18 @@ struct Device {
 	/* GpuPreAgg over resident chunks: the slab merge (and the status read-back)
 	 * of chunk k runs here while chunk k+1 is folded on streams[0] */
 	hipStream_t			merge_stream = nullptr;
+	/* resident-chunk GpuScan (gpuscan_qual_column_resident): per-request slots of
+	 * cursor / error word / work-group ticket in device memory, zeroed once here and
+	 * left zero by each kernel, and the pinned host words its last work-group
+	 * publishes {nitems, errcode} into.  A slot is taken at launch and given back
+	 * when the host has seen its request complete. */
+	static const int	SCAN_SLOTS = 64;
+	kern_gpuscan_slot  *scan_slots = nullptr;
+	cl_uint			   *scan_slots_host = nullptr;		/* SCAN_SLOTS x 16 words */
+	std::mutex			scan_slot_lock;
+	uint64_t			scan_slots_used = 0;
+	int		scan_slot_get();					/* -1: none free */
+	void	scan_slot_put(int slot);
 	std::atomic<unsigned> next_stream{0};
 	BufferPool			pool;
 	PinnedPool			pinned;
@@ -161,6 +173,9 @@ struct strom_task_impl : public strom_task {
 	hipEvent_t	ev[8] = {};
 	int			nev = 0;
 	bool		has_ev_prep = false, has_ev_proj = false;
+	/* resident GpuScan: ev[0] kernel begin, ev[1] kernel done (both on the kernel's own
+	 * dispatch with hipExtModuleLaunchKernel), nothing else */
+	bool		ev_kernel_only = false;
 	/* GpuPreAgg, piped: [0] start [1] head sent (copy-in stream), [2] fold begins [3] fold done
 	 * (streams[0]), [4] merge done [5] status received (merge stream) */
 	bool		ev_preagg_piped = false;

@@ -2740,9 +2740,11 @@ struct gpupreagg_hash_head {
 	 * accumulators are 64 bits wide and are updated by atomics all over the chip): an upper
 	 * bound of |any partial sum in this table|, the sum over the folded chunks of
 	 * rows x 2^(bits of the largest input magnitude).  While it stays below 2^63 nothing can have
-	 * wrapped and nothing is checked.  Two slots: the fold of chunk k reads slot k & 1 and
-	 * (its first work-group) writes the other, which the fold of chunk k + 1 reads -- no
-	 * work-group of a launch reads what another one of it writes.
+	 * wrapped and nothing is checked.  Two slots: the fold of turn k reads slot k & 1 and
+	 * (its first work-group) writes the other, which the fold of turn k + 1 reads -- no
+	 * work-group of a launch reads what another one of it writes.  The host counts a turn
+	 * where it queues the first launch of a request's fold, and every such launch writes
+	 * the other slot, whether it folds (gpupreagg_hash_sum_account) or not (.._sum_carry).
 	 */
 	cl_ulong	sum_bound[2];
 };
@@ -2772,6 +2774,26 @@ gpupreagg_hash_sum_account(kern_gpupreagg *kgpreagg, gpupreagg_hash_head *head, 
 			atomicMax(&kgpreagg->status, (sum_turn & 4u) ? StromError_CpuReCheck : StromError_SumRangeUnproven);
 	}
 	return ok;
+}
+
+/*
+ * a fold that was launched but folds nothing (the check pass raised a row's CpuReCheck) still
+ * takes its turn: the host has advanced the parity when it queued the launch, so the bound as
+ * it stands moves to the slot the next fold reads -- otherwise that fold would read the slot
+ * written two folds ago and the chunk in between would be missing from the bound for good.
+ * The same rule as above: every work-group may read slot turn & 1, the first one writes the other.
+ */
+STROM_DEVICE void
+gpupreagg_hash_sum_carry(gpupreagg_hash_head *head, cl_uint sum_turn)
+{
+	if (gpupreagg_intsum_index(GPUPREAGG_NAGGS) == 0 || (sum_turn & 2u) != 0)
+		return;
+#if !(defined(GPUPREAGG_CHECKED) && GPUPREAGG_CHECKED)
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		head->sum_bound[(sum_turn & 1u) ^ 1u] = head->sum_bound[sum_turn & 1u];
+#else
+	(void)head;				/* every addition is checked one by one: the bound is not kept */
+#endif
 }
 
 STROM_DEVICE char *gpupreagg_hash_rec(char *htab, cl_uint slot)
@@ -3027,7 +3049,10 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 	gpupreagg_hash_lds T;
 
 	if (FOLD && kgpreagg->status != StromError_Success)
+	{
+		gpupreagg_hash_sum_carry(head, sum_turn);
 		return;							/* the check pass found a reason to send the chunk back */
+	}
 	if (FOLD && !gpupreagg_hash_sum_account(kgpreagg, head, sum_turn))
 		return;							/* an integer sum could leave int8: nothing is folded */
 	gpupreagg_load_kparams(KP, kparams, &param_error);
@@ -4084,10 +4109,11 @@ gpupreagg_hash_fold_units(kern_gpupreagg *kgpreagg, char *htab, cl_uint claim_li
 	cl_uint		nunits = (todo ? ntodo : ctl->nunits);
 	cl_int		chunk_status = StromError_Success;	/* (raised by the checked program's additions only) */
 
-	if (kgpreagg->status != StromError_Success)
-		return;
-	if (!GPUPREAGG_PART_RECLEN_OK(kgpreagg, ctl))
-		return;
+	if (kgpreagg->status != StromError_Success || !GPUPREAGG_PART_RECLEN_OK(kgpreagg, ctl))
+	{
+		gpupreagg_hash_sum_carry(head, sum_turn);
+		return;							/* nothing is folded; the bound keeps its turn */
+	}
 	if (!gpupreagg_hash_sum_account(kgpreagg, head, sum_turn))
 		return;							/* an integer sum could leave int8: nothing is folded */
 	gpupreagg_lds_layout_init(L, lds_slots, 1);

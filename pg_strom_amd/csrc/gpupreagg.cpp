@@ -121,7 +121,7 @@ struct strom_gpupreagg {
 	strom_devprog_key	key_checked = 0;
 	Program			   *prog_checked = nullptr;
 	std::atomic<cl_uint> checked_folds{0};	/* (reported: chunks that took the checked program) */
-	cl_uint				sum_turn = 0;		/* hashed: parity of the next fold (gpupreagg_hash_sum_account) */
+	cl_uint				sum_turn = 0;		/* hashed: folds queued so far; its parity is the next fold's (gpupreagg_hash_sum_account) */
 	/* join-as-a-lookup: the program built FOR a column mapping (lookup_program), by its defines */
 	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (lookup_mapping_program) */
 	char			   *d_export_spec = nullptr;	/* preagg_export_spec of this table (fetch on the device) */
@@ -1521,7 +1521,11 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 	 * bound was measured; relaunches for deferred rows add 2 */
 	/* (bit 2 -- "a failed proof is final: CpuReCheck" -- is no longer asked for: the host sends an
 	 * unproven chunk to the exact fold instead, gpupreagg_hashed_exact) */
-	cl_uint		sum_turn = (sess->sum_turn++ & 1u) | ((second && getenv("STROM_GPUPREAGG_HASH_NO_EXACT")) ? 4u : 0u);
+	/* the parity advances where a fold's first launch is queued, below, and nowhere else: that
+	 * launch always writes the slot the next fold reads (gpupreagg_hash_sum_account, or
+	 * gpupreagg_hash_sum_carry when it folds nothing).  A request that queues no fold -- no rows,
+	 * a failure on the way -- leaves the slots alone and so must leave the parity alone */
+	cl_uint		sum_turn = (sess->sum_turn & 1u) | ((second && getenv("STROM_GPUPREAGG_HASH_NO_EXACT")) ? 4u : 0u);
 	if (second)
 	{
 		int rc = hash_sum_refresh(sess);
@@ -1785,6 +1789,8 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 											task->stream, args, nullptr),
 					  "launch gpupreagg hash fold (partitions)");
 			task->pfm.num_kern_exec++;
+			if (turn == 0)
+				sess->sum_turn++;
 			if (!may_defer)
 			{
 				sess->groups_upper += nrows;
@@ -1937,6 +1943,8 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 											task->stream, args, nullptr),
 					  "launch gpupreagg hash fold");
 			task->pfm.num_kern_exec++;
+			if (turn == 0)
+				sess->sum_turn++;
 			if (!may_defer)
 			{
 				sess->groups_upper += todo;

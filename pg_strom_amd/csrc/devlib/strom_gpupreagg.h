@@ -612,6 +612,192 @@ gpupreagg_lds_layout_init(gpupreagg_lds_layout &L, cl_uint G, cl_uint NREP)
 }
 
 /* ---------------------------------------------------------------------- *
+ * dense kernels: shared pieces
+ *
+ * What the streaming dense-id kernels (dense / packed / reg1 / priv _column, and in
+ * part the lookup variants) have in common: where a COLUMN chunk's arrays are, a
+ * tile of them in registers, one row of the tile as a strom_kvars, the row's dense
+ * group id, and the wave reduction that ends the register / lane-private kernels.
+ * ---------------------------------------------------------------------- */
+/* the arrays of the columns the program reads */
+struct gpupreagg_column_source {
+#define X(attno,colidx,NAME)		\
+	const char	   *col_##attno;	\
+	const cl_uint  *nul_##attno;
+	STROM_KVAR_LIST(X)
+#undef X
+	/* a column of the chunk has a NULL bitmap.  Wave-uniform -- it follows from the chunk's
+	 * column directory alone -- so the branch on it that picks the bitmap-free loader
+	 * (GPUPREAGG_TILE_LOAD) is a scalar one */
+	bool			any_nulls;
+};
+
+STROM_DEVICE void
+gpupreagg_column_source_init(gpupreagg_column_source &C, const kern_data_store *kds)
+{
+	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
+
+	C.any_nulls = false;
+#define X(attno,colidx,NAME)													\
+	C.col_##attno = (const char *)kds + coldir[colidx].values_off;				\
+	C.nul_##attno = (coldir[colidx].nulls_off != 0								\
+		? (const cl_uint *)((const char *)kds + coldir[colidx].nulls_off) : NULL);	\
+	C.any_nulls = C.any_nulls || (C.nul_##attno != NULL);
+	STROM_KVAR_LIST(X)
+#undef X
+}
+
+/* one tile: GPUPREAGG_QUADS quads (strom_column_load_quad) per thread and column */
+struct gpupreagg_column_tile {
+#define X(attno,colidx,NAME)											\
+	pg_##NAME##_base_t	v_##attno[GPUPREAGG_QUADS][4];					\
+	cl_uint				nn_##attno[GPUPREAGG_QUADS];
+	STROM_KVAR_LIST(X)
+#undef X
+	int __dummy;
+};
+
+/*
+ * Load the tile of BLOCK * 4 * GPUPREAGG_QUADS rows at tile_base into T; full_tile (uniform): all of
+ * them are below nitems.  The loader is picked per tile by uniform branches (its template
+ * arguments: strom_column_load_quad): a ragged tile checks every row, a full one is
+ * straight-line loads, without the bitmap words when no column has a bitmap, and through the
+ * caches when sibling work-groups of the XCD read the same tile (shared_tiles: several
+ * id-range roles, gpupreagg_dense_column_body).  A caller that passes a literal false there
+ * keeps three loaders, not four.
+ *
+ * A macro that takes T, C, tile_base, nitems and full_tile from the caller's scope under these
+ * names (binding them to macro parameters through locals moved Q1's scalar reloads from 103 to 129:
+ * the call sites name them in a comment instead), and not a function on purpose: as a function (C by reference or by value) the loads are the same, but
+ * the scalar registers are allocated differently around them -- the Q1 program's dense_column sits
+ * at the SGPR limit and reloads half again as many spilled scalars (v_readlane 111 -> 163), and
+ * folds 4 % (decimal columns) to 7 % (numeric images) slower: profiles/dense_shared_pieces_timing.txt
+ */
+#define GPUPREAGG_TILE_LOAD_QUAD(attno,NAME,FULL,NONULL,SHARED)					\
+	strom_column_load_quad<pg_##NAME##_base_t, FULL, NONULL, SHARED>(C.col_##attno, C.nul_##attno,	\
+																	 row0, nitems,		\
+																	 T.v_##attno[k], T.nn_##attno[k]);
+#define GPUPREAGG_TILE_LOAD_SHARED(attno,colidx,NAME)	GPUPREAGG_TILE_LOAD_QUAD(attno,NAME,true,true,true)
+#define GPUPREAGG_TILE_LOAD_NONULL(attno,colidx,NAME)	GPUPREAGG_TILE_LOAD_QUAD(attno,NAME,true,true,false)
+#define GPUPREAGG_TILE_LOAD_FULL(attno,colidx,NAME)		GPUPREAGG_TILE_LOAD_QUAD(attno,NAME,true,false,false)
+#define GPUPREAGG_TILE_LOAD_RAGGED(attno,colidx,NAME)	GPUPREAGG_TILE_LOAD_QUAD(attno,NAME,false,false,false)
+#define GPUPREAGG_TILE_LOAD_AS(BLOCK,COLUMN)									\
+	{																			\
+		_Pragma("unroll")														\
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)								\
+		{																		\
+			cl_uint	row0 = tile_base + (k * (BLOCK) + threadIdx.x) * 4;			\
+			STROM_KVAR_LIST(COLUMN)												\
+		}																		\
+	}
+#define GPUPREAGG_TILE_LOAD(BLOCK,shared_tiles)									\
+	do {																		\
+		if (full_tile && !C.any_nulls && (shared_tiles))						\
+			GPUPREAGG_TILE_LOAD_AS(BLOCK, GPUPREAGG_TILE_LOAD_SHARED)			\
+		else if (full_tile && !C.any_nulls)										\
+			GPUPREAGG_TILE_LOAD_AS(BLOCK, GPUPREAGG_TILE_LOAD_NONULL)			\
+		else if (full_tile)														\
+			GPUPREAGG_TILE_LOAD_AS(BLOCK, GPUPREAGG_TILE_LOAD_FULL)				\
+		else																	\
+			GPUPREAGG_TILE_LOAD_AS(BLOCK, GPUPREAGG_TILE_LOAD_RAGGED)			\
+	} while (0)
+
+/*
+ * Row j of quad k as the program's variables.  A kernel that streams the chunk's own arrays
+ * follows with strom_kvars_from_column(KV, kds, &row_error) and STROM_KVARS_FINISH(KV), where
+ * row_error starts as the parameters' error: it is the error slot the row function goes on
+ * with, and takes what turning a text column's offsets into addresses raises (nothing there
+ * for other programs).
+ */
+STROM_DEVICE void
+gpupreagg_tile_row(strom_kvars &KV, const gpupreagg_column_tile &T, int k, int j)
+{
+#define X(attno,colidx,NAME)													\
+	KV.KVAR_##attno = pg_##NAME##_make(T.v_##attno[k][j], !((T.nn_##attno[k] >> j) & 1));
+	STROM_KVAR_LIST(X)
+#undef X
+}
+
+/*
+ * The row's dense group id: sum over the keys of (key - min) * stride, a NULL key in the slot
+ * behind its range.  Returns true when a key is outside the domain (gid is then no id).
+ * Compacted sessions map the id to a table slot afterwards: gpupreagg_remap_gid, the caller's step.
+ */
+STROM_DEVICE bool
+gpupreagg_dense_gid(const gpupreagg_dense_ctl *ctl, const strom_kparams &KP, const strom_kvars &KV,
+					cl_int *errcode, cl_uint &gid)
+{
+	bool		out_of_domain = false;
+
+	gid = 0;
+#define X(kidx,resno,NAME)															\
+	{																				\
+		pg_##NAME##_t kv = gpupreagg_key_##kidx(errcode, KP, KV);					\
+		cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];					\
+		cl_uint		range = ctl->key_range[kidx];									\
+		cl_uint		off = (kv.isnull ? range : (cl_uint)off64);						\
+		if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))					\
+			out_of_domain = true;													\
+		gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */	\
+	}
+	GPUPREAGG_KEY_LIST(X)
+#undef X
+	return out_of_domain;
+}
+
+STROM_DEVICE cl_ulong
+gpupreagg_shfl_xor_u64(cl_ulong v, int mask)
+{
+	cl_uint lo = __shfl_xor((cl_uint)v, mask, STROM_WAVE);
+	cl_uint hi = __shfl_xor((cl_uint)(v >> 32), mask, STROM_WAVE);
+	return ((cl_ulong)hi << 32) | lo;
+}
+
+/*
+ * Every lane's accumulator v of aggregate <OP, BASE> (the encodings above; NROWS as a count in
+ * 64 bits) is tree-reduced over the wave; lane 0 then folds the result into the LDS image's
+ * vals[g] when apply (wave-uniform) is set.
+ */
+template <int OP, typename BASE>
+STROM_DEVICE void
+gpupreagg_wave_fold(char *vals, cl_uint g, cl_ulong v, bool apply)
+{
+#pragma unroll
+	for (int m = 32; m > 0; m >>= 1)
+	{
+		cl_ulong o = gpupreagg_shfl_xor_u64(v, m);
+		v = (OP == GPUPREAGG_OP_NROWS ? v + o
+			 : gpupreagg_merge8<OP == GPUPREAGG_OP_NROWS ? GPUPREAGG_OP_PSUM : OP, BASE>(v, o));
+	}
+	if (strom_lane_id() != 0 || !apply)
+		return;
+	if (OP == GPUPREAGG_OP_NROWS)
+		__hip_atomic_fetch_add((cl_uint *)vals + g, (cl_uint)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	else if (OP == GPUPREAGG_OP_PSUM)
+	{
+		if (gpupreagg_is_float<BASE>::value)
+			__hip_atomic_fetch_add((cl_double *)vals + g, __longlong_as_double((long long)v),
+								   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		else
+			__hip_atomic_fetch_add((cl_long *)vals + g, (cl_long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	}
+	else if (gpupreagg_is_float<BASE>::value)
+	{
+		if (OP == GPUPREAGG_OP_PMIN)
+			__hip_atomic_fetch_min((cl_ulong *)vals + g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		else
+			__hip_atomic_fetch_max((cl_ulong *)vals + g, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	}
+	else
+	{
+		if (OP == GPUPREAGG_OP_PMIN)
+			__hip_atomic_fetch_min((cl_long *)vals + g, (cl_long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+		else
+			__hip_atomic_fetch_max((cl_long *)vals + g, (cl_long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+	}
+}
+
+/* ---------------------------------------------------------------------- *
  * one row: qual, group id, fold
  * ---------------------------------------------------------------------- */
 STROM_DEVICE void
@@ -622,8 +808,7 @@ gpupreagg_dense_row(char *lds, const gpupreagg_dense_ctl *ctl, const gpupreagg_l
 					bool qual_done = false)
 {
 	cl_int		errcode = param_error;
-	cl_uint		gid = 0;
-	bool		out_of_domain = false;
+	cl_uint		gid;
 
 	if (!qual_done)				/* (the caller may have seen the qual pass, without an error) */
 	{
@@ -631,19 +816,7 @@ gpupreagg_dense_row(char *lds, const gpupreagg_dense_ctl *ctl, const gpupreagg_l
 		if (errcode == StromError_Success && !EVAL(rc))
 			return;
 	}
-	/* group id: dense, NULL key in its own slot */
-#define X(kidx,resno,NAME)															\
-	{																				\
-		pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);					\
-		cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];					\
-		cl_uint		range = ctl->key_range[kidx];									\
-		cl_uint		off = (kv.isnull ? range : (cl_uint)off64);						\
-		if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))					\
-			out_of_domain = true;													\
-		gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */											\
-	}
-	GPUPREAGG_KEY_LIST(X)
-#undef X
+	bool		out_of_domain = gpupreagg_dense_gid(ctl, KP, KV, &errcode, gid);
 	if (!out_of_domain && !gpupreagg_remap_gid(ctl, gid))
 		out_of_domain = true;
 	/*
@@ -860,8 +1033,7 @@ gpupreagg_packed_row(char *lds, const gpupreagg_dense_ctl *ctl, const gpupreagg_
 					 bool qual_done = false)
 {
 	cl_int		errcode = param_error;
-	cl_uint		gid = 0;
-	bool		out_of_domain = false;
+	cl_uint		gid;
 
 	if (!qual_done)
 	{
@@ -869,18 +1041,8 @@ gpupreagg_packed_row(char *lds, const gpupreagg_dense_ctl *ctl, const gpupreagg_
 		if (errcode == StromError_Success && !EVAL(rc))
 			return;
 	}
-#define X(kidx,resno,NAME)															\
-	{																				\
-		pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);					\
-		cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];					\
-		cl_uint		range = ctl->key_range[kidx];									\
-		cl_uint		off = (kv.isnull ? range : (cl_uint)off64);						\
-		if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))					\
-			out_of_domain = true;													\
-		gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */											\
-	}
-	GPUPREAGG_KEY_LIST(X)
-#undef X
+	/* (no gpupreagg_remap_gid: the host packs no chunk of a compacted session -- packed_plan) */
+	bool		out_of_domain = gpupreagg_dense_gid(ctl, KP, KV, &errcode, gid);
 	if (errcode == StromError_Success && !out_of_domain && gid - gid_lo >= G)
 		return;							/* another role's slice of the id range */
 	if (errcode != StromError_Success)
@@ -1006,15 +1168,6 @@ gpupreagg_store_slab_packed(char *lds, const gpupreagg_pack_ctl *pk, char *slab,
 }
 #endif	/* GPUPREAGG_PACKABLE */
 
-struct gpupreagg_column_tile {
-#define X(attno,colidx,NAME)											\
-	pg_##NAME##_base_t	v_##attno[GPUPREAGG_QUADS][4];					\
-	cl_uint				nn_##attno[GPUPREAGG_QUADS];
-	STROM_KVAR_LIST(X)
-#undef X
-	int __dummy;
-};
-
 STROM_DEVICE void
 gpupreagg_load_kparams(strom_kparams &KP, const kern_parambuf *kparams, cl_int *errcode)
 {
@@ -1052,7 +1205,6 @@ gpupreagg_dense_column_body(kern_gpupreagg *kgpreagg,
 	const gpupreagg_dense_ctl ctl_by_value = *ctl_in_memory;
 	const gpupreagg_dense_ctl *ctl = &ctl_by_value;
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
 	cl_uint		nitems = kds->nitems;
 	cl_uint		ntiles = (nitems + GPUPREAGG_TILE_ROWS - 1) / GPUPREAGG_TILE_ROWS;
 	cl_uint		nsplits = ctl->nsplits;
@@ -1105,18 +1257,10 @@ gpupreagg_dense_column_body(kern_gpupreagg *kgpreagg,
 		gpupreagg_lds_init(lds, L, G, NREP);
 	}
 
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (const char *)kds + coldir[colidx].values_off;	\
-	const cl_uint *nul_##attno = (coldir[colidx].nulls_off != 0					\
-		? (const cl_uint *)((const char *)kds + coldir[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
-	bool		any_nulls = false;		/* wave-uniform: picks the bitmap-free loader */
-#define X(attno,colidx,NAME)	any_nulls = any_nulls || (nul_##attno != NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	gpupreagg_column_source C;
+	gpupreagg_column_source_init(C, kds);
 	const cl_uint rowflags = (KERN_GPUPREAGG_ZONE_BOUNDED(kgpreagg) ? ROWFLAG_ZONE_BOUNDED : 0u) |
-		(any_nulls ? 0u : ROWFLAG_ALL_NOTNULL);
+		(C.any_nulls ? 0u : ROWFLAG_ALL_NOTNULL);
 
 	char	   *my_slab = slabs + (size_t)(wg_in_split * nsplits + split) * ctl->slab_bytes;
 #if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
@@ -1133,63 +1277,8 @@ gpupreagg_dense_column_body(kern_gpupreagg *kgpreagg,
 		bool		full_tile = (tile_base + GPUPREAGG_TILE_ROWS <= nitems);
 		gpupreagg_column_tile T;
 
-
-		if (full_tile && !any_nulls && shared_tiles)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true, true, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else if (full_tile && !any_nulls)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else if (full_tile)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, false>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
+		/* (reads C, tile_base, nitems, full_tile; fills T) */
+		GPUPREAGG_TILE_LOAD(GPUPREAGG_BLOCK, shared_tiles);
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
@@ -1200,13 +1289,7 @@ gpupreagg_dense_column_body(kern_gpupreagg *kgpreagg,
 				if (full_tile || row0 + j < nitems)
 				{
 					strom_kvars	KV;
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = pg_##NAME##_make(T.v_##attno[k][j],			\
-													   !((T.nn_##attno[k] >> j) & 1));
-					STROM_KVAR_LIST(X)
-#undef X
-					/* (the row's error slot starts as the parameters' and takes what turning a text
-					 * column's offsets into addresses raises; nothing there for other programs) */
+					gpupreagg_tile_row(KV, T, k, j);
 					cl_int		row_error = param_error;
 					strom_kvars_from_column(KV, kds, &row_error);
 					STROM_KVARS_FINISH(KV);
@@ -1512,20 +1595,8 @@ gpupreagg_dense_joined(kern_gpupreagg *kgpreagg,
 			 * from the columns the keys read -- gather the others only for the
 			 * role's own rows (gpupreagg_dense_row decides again, with errors) */
 			cl_int		e2 = errcode;
-			cl_uint		gid = 0;
-			bool		out_of_domain = false;
-#define Y(kidx,resno,NAME)														\
-			{																	\
-				pg_##NAME##_t kv = gpupreagg_key_##kidx(&e2, KP, KV);			\
-				cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];		\
-				cl_uint		range = ctl->key_range[kidx];						\
-				cl_uint		off = (kv.isnull ? range : (cl_uint)off64);			\
-				if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))		\
-					out_of_domain = true;										\
-				gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */								\
-			}
-			GPUPREAGG_KEY_LIST(Y)
-#undef Y
+			cl_uint		gid;
+			bool		out_of_domain = gpupreagg_dense_gid(ctl, KP, KV, &e2, gid);
 			if (e2 == StromError_Success && !out_of_domain &&
 				gpupreagg_remap_gid(ctl, gid) && gid - gid_lo >= G)
 				continue;
@@ -1903,11 +1974,7 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 				if (!((gone[k] >> j) & 1))
 				{
 					strom_kvars	KV;
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = pg_##NAME##_make(T.v_##attno[k][j],			\
-													   !((T.nn_##attno[k] >> j) & 1));
-					STROM_KVAR_LIST(X)
-#undef X
+					gpupreagg_tile_row(KV, T, k, j);
 					STROM_KVARS_FINISH(KV);
 #if GPUPREAGG_ABLATE & 1
 					/* (measurement only: nothing is accumulated) */
@@ -2039,23 +2106,11 @@ gpupreagg_reg_row(gpupreagg_reg_state<NG> &S, const gpupreagg_dense_ctl *ctl,
 {
 	cl_int		errcode = param_error;
 	pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
-	cl_uint		gid = 0;
-	bool		out_of_domain = false;
+	cl_uint		gid;
 
 	if (errcode == StromError_Success && !EVAL(rc))
 		return;
-#define X(kidx,resno,NAME)															\
-	{																				\
-		pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);					\
-		cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];					\
-		cl_uint		range = ctl->key_range[kidx];									\
-		cl_uint		off = (kv.isnull ? range : (cl_uint)off64);						\
-		if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))					\
-			out_of_domain = true;													\
-		gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */											\
-	}
-	GPUPREAGG_KEY_LIST(X)
-#undef X
+	bool		out_of_domain = gpupreagg_dense_gid(ctl, KP, KV, &errcode, gid);
 	if (!out_of_domain && !gpupreagg_remap_gid(ctl, gid))
 		out_of_domain = true;
 #define X(aidx,resno,OP,NAME)														\
@@ -2108,21 +2163,12 @@ gpupreagg_reg_row(gpupreagg_reg_state<NG> &S, const gpupreagg_dense_ctl *ctl,
 		S.flags[g] |= (gid == (cl_uint)g ? need : 0u);
 }
 
-STROM_DEVICE cl_ulong
-gpupreagg_shfl_xor_u64(cl_ulong v, int mask)
-{
-	cl_uint lo = __shfl_xor((cl_uint)v, mask, STROM_WAVE);
-	cl_uint hi = __shfl_xor((cl_uint)(v >> 32), mask, STROM_WAVE);
-	return ((cl_ulong)hi << 32) | lo;
-}
-
 template <int NG>
 __device__ __forceinline__ void
 gpupreagg_reg_kernel_body(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 						  const gpupreagg_dense_ctl *ctl, char *slabs, char *lds)
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
 	cl_uint		nitems = kds->nitems;
 	cl_uint		ntiles = (nitems + GPUPREAGG_REG_TILE_ROWS - 1) / GPUPREAGG_REG_TILE_ROWS;
 	cl_uint		G = ctl->groups_per_split;
@@ -2160,16 +2206,8 @@ gpupreagg_reg_kernel_body(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 		GPUPREAGG_AGG_LIST(X)
 #undef X
 	}
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (const char *)kds + coldir[colidx].values_off;	\
-	const cl_uint *nul_##attno = (coldir[colidx].nulls_off != 0					\
-		? (const cl_uint *)((const char *)kds + coldir[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
-	bool		any_nulls = false;		/* wave-uniform: picks the bitmap-free loader */
-#define X(attno,colidx,NAME)	any_nulls = any_nulls || (nul_##attno != NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	gpupreagg_column_source C;
+	gpupreagg_column_source_init(C, kds);
 	const cl_uint rowflags = (KERN_GPUPREAGG_ZONE_BOUNDED(kgpreagg) ? ROWFLAG_ZONE_BOUNDED : 0u);
 	for (cl_uint tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
 	{
@@ -2177,48 +2215,9 @@ gpupreagg_reg_kernel_body(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 		bool		full_tile = (tile_base + GPUPREAGG_REG_TILE_ROWS <= nitems);
 		gpupreagg_column_tile T;
 
-		if (full_tile && !any_nulls)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else if (full_tile)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, false>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
+		/* (one work-group per tile stream: no sibling shares a tile) */
+		/* (reads C, tile_base, nitems, full_tile; fills T) */
+		GPUPREAGG_TILE_LOAD(GPUPREAGG_REG_BLOCK, false);
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
@@ -2229,11 +2228,7 @@ gpupreagg_reg_kernel_body(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 				if (full_tile || row0 + j < nitems)
 				{
 					strom_kvars	KV;
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = pg_##NAME##_make(T.v_##attno[k][j],			\
-													   !((T.nn_##attno[k] >> j) & 1));
-					STROM_KVAR_LIST(X)
-#undef X
+					gpupreagg_tile_row(KV, T, k, j);
 					cl_int		row_error = param_error;
 					strom_kvars_from_column(KV, kds, &row_error);
 					STROM_KVARS_FINISH(KV);
@@ -2251,56 +2246,9 @@ gpupreagg_reg_kernel_body(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 		for (int m = 32; m > 0; m >>= 1)
 			flags |= __shfl_xor(flags, m, STROM_WAVE);
 #define X(aidx,resno,OP,NAME)															\
-		{																				\
-			cl_ulong v = S.v_##aidx[g];													\
-			_Pragma("unroll")															\
-			for (int m = 32; m > 0; m >>= 1)											\
-			{																			\
-				cl_ulong o = gpupreagg_shfl_xor_u64(v, m);								\
-				v = (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS ? v + o					\
-					 : gpupreagg_merge8<GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS			\
-										? GPUPREAGG_OP_PSUM : GPUPREAGG_OP_##OP,		\
-										pg_##NAME##_base_t>(v, o));						\
-			}																			\
-			if (strom_lane_id() == 0 && (cl_uint)g < G)									\
-			{																			\
-				char *slot = lds + L.vals_off[aidx];									\
-				if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS)							\
-					__hip_atomic_fetch_add((cl_uint *)slot + g, (cl_uint)v,				\
-										   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-				else if (flags & (2u << aidx))											\
-				{																		\
-					if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PSUM)							\
-					{																	\
-						if (gpupreagg_is_float<pg_##NAME##_base_t>::value)				\
-							__hip_atomic_fetch_add((cl_double *)slot + g,				\
-												   __longlong_as_double((long long)v),	\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_add((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-					else if (gpupreagg_is_float<pg_##NAME##_base_t>::value)				\
-					{																	\
-						if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PMIN)						\
-							__hip_atomic_fetch_min((cl_ulong *)slot + g, v,				\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_max((cl_ulong *)slot + g, v,				\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-					else																\
-					{																	\
-						if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PMIN)						\
-							__hip_atomic_fetch_min((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_max((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-				}																		\
-			}																			\
-		}
+		gpupreagg_wave_fold<GPUPREAGG_OP_##OP, pg_##NAME##_base_t>						\
+			(lds + L.vals_off[aidx], g, S.v_##aidx[g],									\
+			 (cl_uint)g < G && (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS || (flags & (2u << aidx))));
 		GPUPREAGG_AGG_LIST(X)
 #undef X
 		if (strom_lane_id() == 0 && (cl_uint)g < G && flags != 0)
@@ -2348,23 +2296,11 @@ gpupreagg_priv_row(char *lds, gpupreagg_priv_state &S, const gpupreagg_dense_ctl
 {
 	cl_int		errcode = param_error;
 	pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
-	cl_uint		gid = 0;
-	bool		out_of_domain = false;
+	cl_uint		gid;
 
 	if (errcode == StromError_Success && !EVAL(rc))
 		return;
-#define X(kidx,resno,NAME)															\
-	{																				\
-		pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);					\
-		cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];					\
-		cl_uint		range = ctl->key_range[kidx];									\
-		cl_uint		off = (kv.isnull ? range : (cl_uint)off64);						\
-		if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))					\
-			out_of_domain = true;													\
-		gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */											\
-	}
-	GPUPREAGG_KEY_LIST(X)
-#undef X
+	bool		out_of_domain = gpupreagg_dense_gid(ctl, KP, KV, &errcode, gid);
 	if (!out_of_domain && !gpupreagg_remap_gid(ctl, gid))
 		out_of_domain = true;
 #define X(aidx,resno,OP,NAME)														\
@@ -2441,7 +2377,6 @@ gpupreagg_priv_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 	const gpupreagg_dense_ctl *ctl = &ctl_by_value;
 
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
 	cl_uint		nitems = kds->nitems;
 	cl_uint		ntiles = (nitems + GPUPREAGG_REG_TILE_ROWS - 1) / GPUPREAGG_REG_TILE_ROWS;
 	cl_uint		G = ctl->groups_per_split;		/* 2 .. 32, one split */
@@ -2484,16 +2419,8 @@ gpupreagg_priv_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 #undef X
 	}
 	__syncthreads();
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (const char *)kds + coldir[colidx].values_off;	\
-	const cl_uint *nul_##attno = (coldir[colidx].nulls_off != 0					\
-		? (const cl_uint *)((const char *)kds + coldir[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
-	bool		any_nulls = false;		/* wave-uniform: picks the bitmap-free loader */
-#define X(attno,colidx,NAME)	any_nulls = any_nulls || (nul_##attno != NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	gpupreagg_column_source C;
+	gpupreagg_column_source_init(C, kds);
 	const cl_uint rowflags = (KERN_GPUPREAGG_ZONE_BOUNDED(kgpreagg) ? ROWFLAG_ZONE_BOUNDED : 0u);
 	for (cl_uint tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
 	{
@@ -2501,48 +2428,9 @@ gpupreagg_priv_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 		bool		full_tile = (tile_base + GPUPREAGG_REG_TILE_ROWS <= nitems);
 		gpupreagg_column_tile T;
 
-		if (full_tile && !any_nulls)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else if (full_tile)
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, true>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
-		else
-		{
-#pragma unroll
-			for (int k = 0; k < GPUPREAGG_QUADS; k++)
-			{
-				cl_uint	row0 = tile_base + (k * GPUPREAGG_REG_BLOCK + threadIdx.x) * 4;
-#define X(attno,colidx,NAME)													\
-				strom_column_load_quad<pg_##NAME##_base_t, false>(col_##attno, nul_##attno,	\
-														   row0, nitems,				\
-														   T.v_##attno[k], T.nn_##attno[k]);
-				STROM_KVAR_LIST(X)
-#undef X
-			}
-		}
+		/* (one work-group per tile stream: no sibling shares a tile) */
+		/* (reads C, tile_base, nitems, full_tile; fills T) */
+		GPUPREAGG_TILE_LOAD(GPUPREAGG_REG_BLOCK, false);
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
@@ -2553,11 +2441,7 @@ gpupreagg_priv_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 				if (full_tile || row0 + j < nitems)
 				{
 					strom_kvars	KV;
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = pg_##NAME##_make(T.v_##attno[k][j],			\
-													   !((T.nn_##attno[k] >> j) & 1));
-					STROM_KVAR_LIST(X)
-#undef X
+					gpupreagg_tile_row(KV, T, k, j);
 					cl_int		row_error = param_error;
 					strom_kvars_from_column(KV, kds, &row_error);
 					STROM_KVARS_FINISH(KV);
@@ -2591,56 +2475,11 @@ gpupreagg_priv_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 			cl_ulong v = (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS						\
 						  ? (cl_ulong)((const cl_uint *)(lds + S.poff[aidx]))[idx]		\
 						  : ((const cl_ulong *)(lds + S.poff[aidx]))[idx]);				\
-			_Pragma("unroll")															\
-			for (int m = 32; m > 0; m >>= 1)											\
-			{																			\
-				cl_ulong o = gpupreagg_shfl_xor_u64(v, m);								\
-				v = (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS ? v + o					\
-					 : gpupreagg_merge8<GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS			\
-										? GPUPREAGG_OP_PSUM : GPUPREAGG_OP_##OP,		\
-										pg_##NAME##_base_t>(v, o));						\
-			}																			\
 			bool has = (GPUPREAGG_OP_##OP != GPUPREAGG_OP_NROWS && ((S.has[aidx] >> g) & 1));	\
 			if (has)																	\
 				flags |= (2u << aidx);													\
-			if (strom_lane_id() == 0)													\
-			{																			\
-				char *slot = lds + L.vals_off[aidx];									\
-				if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS)							\
-					__hip_atomic_fetch_add((cl_uint *)slot + g, (cl_uint)v,				\
-										   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-				else if (has)															\
-				{																		\
-					if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PSUM)							\
-					{																	\
-						if (gpupreagg_is_float<pg_##NAME##_base_t>::value)				\
-							__hip_atomic_fetch_add((cl_double *)slot + g,				\
-												   __longlong_as_double((long long)v),	\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_add((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-					else if (gpupreagg_is_float<pg_##NAME##_base_t>::value)				\
-					{																	\
-						if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PMIN)						\
-							__hip_atomic_fetch_min((cl_ulong *)slot + g, v,				\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_max((cl_ulong *)slot + g, v,				\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-					else																\
-					{																	\
-						if (GPUPREAGG_OP_##OP == GPUPREAGG_OP_PMIN)						\
-							__hip_atomic_fetch_min((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-						else															\
-							__hip_atomic_fetch_max((cl_long *)slot + g, (cl_long)v,		\
-												   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);	\
-					}																	\
-				}																		\
-			}																			\
+			gpupreagg_wave_fold<GPUPREAGG_OP_##OP, pg_##NAME##_base_t>					\
+				(lds + L.vals_off[aidx], g, v, GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS || has);	\
 		}
 		GPUPREAGG_AGG_LIST(X)
 #undef X
@@ -4754,8 +4593,7 @@ gpupreagg_census_body(const kern_gpupreagg *kgpreagg, const kern_data_store *kds
 		cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
 		strom_kvars	KV;
 		cl_int		errcode = param_error;
-		cl_uint		gid = 0;
-		bool		out_of_domain = false;
+		cl_uint		gid;
 		const HeapTupleHeaderData *htup = NULL;
 		if (!is_column && row_family)
 			htup = strom_locate_tuple(kds, chunk_format, kds_index);
@@ -4772,20 +4610,8 @@ gpupreagg_census_body(const kern_gpupreagg *kgpreagg, const kern_data_store *kds
 		pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
 		if (errcode == StromError_Success && !EVAL(rc))
 			continue;
-#define X(kidx,resno,NAME)															\
-		{																			\
-			pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);				\
-			cl_long		off64 = (cl_long)kv.value - ctl->key_min[kidx];				\
-			cl_uint		range = ctl->key_range[kidx];								\
-			cl_uint		off = (kv.isnull ? range : (cl_uint)off64);					\
-			if (!kv.isnull && (off64 < 0 || off64 >= (cl_long)range))				\
-				out_of_domain = true;												\
-			gid += (kidx == 0 ? off : off * ctl->key_stride[kidx]);	/* (stride 0 is 1) */										\
-		}
-		GPUPREAGG_KEY_LIST(X)
-#undef X
-		if (out_of_domain)
-			continue;				/* the fold reports it */
+		if (gpupreagg_dense_gid(ctl, KP, KV, &errcode, gid))
+			continue;				/* a key outside the domain: the fold reports it */
 		cl_uint		bit = 1u << (gid & 31);
 		if (!(bitmap[gid >> 5] & bit))
 			atomicOr(&bitmap[gid >> 5], bit);

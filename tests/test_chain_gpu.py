@@ -326,13 +326,12 @@ def test_preagg_straight_over_the_join_result_pairs(ngroups):
     assert np.array_equal(gmax[order][~np.isinf(wmax)], wmax[~np.isinf(wmax)])
 
 
-@pytest.mark.parametrize("ngroups,keytype", [(53, "int4"), (9000, "int4"), (53, "int8")])
-def test_join_as_a_lookup_inside_the_aggregate(ngroups, keytype):
-    """strom_submit_gpupreagg_lookup: fact JOIN dim WHERE ... GROUP BY in ONE pass over
-    the fact chunk -- no join request, no result pairs; rows without a partner (NULL key,
-    key outside the table, empty slot) are dropped, the WHERE is the aggregate's qual"""
+def lookup_aggregate_against_numpy(n, ngroups, keytype, fact_nulls=True):
+    """n fact rows JOIN a 20000-row dimension GROUP BY through strom_submit_gpupreagg_lookup, two
+    chunks into the same table, against numpy over the joined rows.  fact_nulls: the fact chunk's
+    key and int4 columns carry NULL bitmaps (the dimension's columns have NULLs either way)."""
     runtime.init()
-    n, nd = 250007, 20000
+    nd = 20000
     rng = np.random.default_rng(89)
     span = int(nd * 1.3)
     fk = rng.integers(-50, span + 50, n).astype(np.int32)      # also keys below / above the table
@@ -340,9 +339,12 @@ def test_join_as_a_lookup_inside_the_aggregate(ngroups, keytype):
     a = rng.integers(0, 2**31, n, dtype=np.int64).astype(np.int32)
     an = rng.random(n) < 0.03
     b = rng.random(n)
+    if not fact_nulls:
+        fkn[:] = False
+        an[:] = False
     kdt = np.int32 if keytype == "int4" else np.int64
-    fact = kds.build_kds("column", [kds.Column(keytype, fk.astype(kdt), fkn), kds.Column("int4", a, an),
-                                    kds.Column("float8", b)])
+    fact = kds.build_kds("column", [kds.Column(keytype, fk.astype(kdt), fkn if fact_nulls else None),
+                                    kds.Column("int4", a, an if fact_nulls else None), kds.Column("float8", b)])
     dkey = rng.permutation(span)[:nd].astype(np.int32)         # holes in the key range
     dgrp = (dkey % ngroups).astype(np.int32)
     dgn = rng.random(nd) < 0.04
@@ -391,6 +393,14 @@ def test_join_as_a_lookup_inside_the_aggregate(ngroups, keytype):
     gmax, gnull = pr.column(4)
     assert np.array_equal(gnull[order], np.isinf(wmax))
     assert np.array_equal(gmax[order][~np.isinf(wmax)], wmax[~np.isinf(wmax)])
+
+
+@pytest.mark.parametrize("ngroups,keytype", [(53, "int4"), (9000, "int4"), (53, "int8")])
+def test_join_as_a_lookup_inside_the_aggregate(ngroups, keytype):
+    """strom_submit_gpupreagg_lookup: fact JOIN dim WHERE ... GROUP BY in ONE pass over
+    the fact chunk -- no join request, no result pairs; rows without a partner (NULL key,
+    key outside the table, empty slot) are dropped, the WHERE is the aggregate's qual"""
+    lookup_aggregate_against_numpy(250007, ngroups, keytype)
 
 
 @pytest.mark.parametrize("epochs,narrow,generic", [(False, True, False), (True, True, False), (False, False, False),

@@ -247,7 +247,8 @@ def test_id_range_split_over_workgroup_roles(monkeypatch):
 def c4_table(n, seed, ngroups, xlo=-10**6, xhi=10**6, nulls=None):
     rng = np.random.default_rng(seed)
     g = rng.integers(0, ngroups, n).astype(np.int32)
-    g[:ngroups] = np.arange(ngroups, dtype=np.int32)           # every group occurs
+    k = min(n, ngroups)
+    g[:k] = np.arange(k, dtype=np.int32)                        # every group occurs (as far as n rows go)
     x = rng.integers(xlo, xhi, n).astype(np.int32)
     y = rng.random(n) * 100
     return [kds.Column("int4", g), kds.Column("int4", x, None if nulls is None else rng.random(n) < nulls),

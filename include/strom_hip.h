@@ -458,9 +458,20 @@ strom_task *strom_submit_gpuhashjoin_projection(strom_hashjoin_table *tbl,
  * src_colidx[r] (0-based) of relation src_depth[r]; type_oids[r] gives its
  * width, which must equal the source's (StromError_DataStoreCorruption
  * otherwise); a NEGATIVE oid means "that type, no zone map needed" and
- * spares the min/max pass over the column.  Fixed-width by-value columns.
- * Inner columns of a single-relation table with a DIRECT index and unique
- * keys are served from slot-indexed arrays the table builds on first use.
+ * spares the min/max pass over the column.  Fixed-width by-value columns
+ * (bool, int2/4/8, float4/8, date, time, timestamp, the 64-bit numeric forms,
+ * char(1)) and STROM_TEXTOID / STROM_BPCHARNOID.  A text or character(n)
+ * column of the result has attlen -1, attbyval 0, attalign 4: its array
+ * holds each row's 8-byte offset from the chunk head (0: NULL), the datums
+ * -- copied whole, header included, whatever their form -- start on 4-byte
+ * boundaries in a heap area behind the column arrays (extra_off), sized
+ * exactly by a counting kernel that runs first; such a column has no zone
+ * map.  Its source must be a text column too (DataStoreCorruption
+ * otherwise, also for a source datum that points beyond its chunk); a
+ * TUPSLOT 'outer' as its source answers BadRequestMessage; a result beyond
+ * 4 GB answers DataStoreOutOfRange.
+ * Fixed-width inner columns of a single-relation table with a DIRECT index and
+ * unique keys are served from slot-indexed arrays the table builds on first use.
  * A join that ended with
  * StromError_DataStoreNoSpace is reported as such: resize, join again.
  */

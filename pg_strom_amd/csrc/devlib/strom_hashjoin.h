@@ -1740,18 +1740,198 @@ hashjoin_dimrec_narrow_kernel(const hashjoin_dimrec_spec *spec, const char *recs
 #define HASHJOIN_PROJ_MAXCOLS	64
 #define HASHJOIN_PROJ_ROWS		4
 
+/*
+ * A text / character(n) destination column (attlen -1): where one record's datum lies.  The
+ * source is described once per column (hashjoin_proj_text_source), the datum found per record
+ * (hashjoin_proj_text_datum); the sizing pass and the projection both go through these two, so
+ * they cannot disagree about a datum.  A COLUMN outer chunk gives the datum's 8-byte offset (0 is
+ * NULL, and the bitmap says so too); heap tuples -- ROW / ROW_FLAT outer chunks, the hash
+ * entries of an inner relation -- go through the tuple accessors (a text column has a usable
+ * attcacheoff only as the first varlena; the accessor knows).
+ */
+struct hashjoin_proj_textsrc {
+	cl_int		kind;			/* 0: nothing readable (the mapping does not fit), 1: COLUMN outer chunk,
+								 * 2: ROW / ROW_FLAT outer chunk, 3: inner relation */
+	cl_int		depth;
+	cl_int		col;
+	cl_uint		values_off;		/* kind 1 */
+	cl_uint		nulls_off;
+	const kern_hashtable *kht;	/* kind 3 */
+};
+
+STROM_DEVICE hashjoin_proj_textsrc
+hashjoin_proj_text_source(const kern_data_store *kds, const kern_multihash *kmhash,
+						  cl_uint nrels, cl_int depth, cl_int col)
+{
+	hashjoin_proj_textsrc	ts;
+
+	ts.kind = 0;
+	ts.depth = depth;
+	ts.col = col;
+	ts.values_off = 0;
+	ts.nulls_off = 0;
+	ts.kht = NULL;
+	if (depth == 0)
+	{
+		/* a by-value source column is never followed as an address */
+		if (col < 0 || col >= (cl_int)kds->ncols || kds->colmeta[col].attlen >= 0)
+			return ts;
+		if (kds->format == KDS_FORMAT_COLUMN)
+		{
+			const kern_coldir *sd = KERN_DATA_STORE_COLDIR(kds) + col;
+			ts.kind = 1;
+			ts.values_off = sd->values_off;
+			ts.nulls_off = sd->nulls_off;
+		}
+		else if (kds->format == KDS_FORMAT_ROW || kds->format == KDS_FORMAT_ROW_FLAT)
+			ts.kind = 2;
+	}
+	else if (depth > 0 && depth < (cl_int)nrels)
+	{
+		const kern_hashtable *kht = KERN_HASHTABLE(kmhash, depth - 1);
+		if (col >= 0 && col < (cl_int)kht->ncols && kht->colmeta[col].attlen < 0)
+		{
+			ts.kind = 3;
+			ts.kht = kht;
+		}
+	}
+	return ts;
+}
+
+/* the datum's address and size, or NULL for SQL NULL; *p_bad when it cannot be read: the mapping
+ * does not fit, or a COLUMN offset / header points beyond the source chunk */
+STROM_DEVICE const char *
+hashjoin_proj_text_datum(const hashjoin_proj_textsrc &ts, const kern_data_store *kds,
+						 const kern_data_store *ktoast, cl_uint outer_row, const cl_int *rbuf,
+						 cl_uint *p_size, bool *p_bad)
+{
+	const char *addr = NULL;
+
+	*p_size = 0;
+	if (ts.kind == 1)
+	{
+		cl_ulong	length = kds->length;
+		if (outer_row >= kds->nitems)
+		{
+			*p_bad = true;
+			return NULL;
+		}
+		if (ts.nulls_off != 0)
+		{
+			const cl_uint *nn = (const cl_uint *)((const char *)kds + ts.nulls_off);
+			if (!((nn[outer_row >> 5] >> (outer_row & 31)) & 1))
+				return NULL;
+		}
+		cl_ulong	voff = ((const cl_ulong *)((const char *)kds + ts.values_off))[outer_row];
+		if (voff == 0)
+			return NULL;
+		/* the header inside the chunk before it is read, the datum before it is copied */
+		if (voff >= length)
+		{
+			*p_bad = true;
+			return NULL;
+		}
+		cl_uchar	b0 = *((const cl_uchar *)kds + voff);
+		cl_uint		hdr = (b0 == 0x01 ? 2u : (b0 & 0x01) ? 1u : 4u);
+		if (voff + hdr > length)
+		{
+			*p_bad = true;
+			return NULL;
+		}
+		addr = (const char *)kds + voff;
+		cl_uint		sz = strom_varsize_any(addr);
+		if (sz < hdr || voff + sz > length)
+		{
+			*p_bad = true;
+			return NULL;
+		}
+		*p_size = sz;
+		return addr;
+	}
+	if (ts.kind == 2)
+		addr = (const char *)kern_get_datum(kds, ktoast, ts.col, outer_row);
+	else if (ts.kind == 3)
+	{
+		const kern_hashentry *ent = (const kern_hashentry *)((const char *)ts.kht + rbuf[ts.depth]);
+		addr = kern_get_datum_tuple(ts.kht->colmeta, &ent->htup, ts.col);
+	}
+	else
+		*p_bad = true;
+	if (addr)
+	{
+		cl_uint		sz = strom_varsize_any(addr);
+		if (sz < 1)
+		{
+			*p_bad = true;
+			return NULL;
+		}
+		*p_size = sz;
+	}
+	return addr;
+}
+
+/*
+ * First of two passes when the destination has text columns: the heap area's size is not known
+ * to the host (an inner datum is repeated once per joined row), so this kernel adds up, per text
+ * column, the 4-byte rounded sizes of the datums the projection will copy.  One wave reduction
+ * and one 64-bit atomic per wave and column; none when the wave's sum is 0.
+ */
 extern "C" __global__ void
 __launch_bounds__(256)
-gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
-							  const kern_multihash *kmhash,
-							  const kern_data_store *kds,
-							  const kern_data_store *ktoast,
-							  kern_data_store *dst,
-							  const cl_int *src_depth,
-							  const cl_int *src_colidx,
-							  cl_uint *col_has_null,		/* [ncols] flags, then one failure flag */
-							  const hashjoin_index *hjidx,
-							  const cl_ulong *dimptr)		/* [2 * ncols] slot-indexed values / isnull arrays, or 0 */
+gpuhashjoin_projection_column_textsize(kern_hashjoin *khashjoin,
+									   const kern_multihash *kmhash,
+									   const kern_data_store *kds,
+									   const kern_data_store *ktoast,
+									   cl_uint nitems,
+									   cl_uint ncols,
+									   const cl_int *src_depth,
+									   const cl_int *src_colidx,
+									   const cl_int *dst_attlen,	/* [ncols] */
+									   cl_ulong *totals,			/* [ncols] */
+									   cl_uint *p_failed)
+{
+	kern_resultbuf *kresults = KERN_HASHJOIN_RESULTBUF(khashjoin);
+	cl_uint		nrels = kresults->nrels;
+	bool		bad = false;
+
+	for (cl_uint r = 0; r < ncols; r++)
+	{
+		if (dst_attlen[r] >= 0)
+			continue;
+		hashjoin_proj_textsrc ts = hashjoin_proj_text_source(kds, kmhash, nrels, src_depth[r], src_colidx[r]);
+		cl_ulong	sum = 0;
+		for (cl_uint idx = blockIdx.x * blockDim.x + threadIdx.x;
+			 idx < nitems;
+			 idx += gridDim.x * blockDim.x)
+		{
+			const cl_int *rbuf = kresults->results + (size_t)nrels * idx;
+			cl_uint		sz;
+			if (hashjoin_proj_text_datum(ts, kds, ktoast, (cl_uint)(rbuf[0] - 1), rbuf, &sz, &bad))
+				sum += ((cl_ulong)sz + 3UL) & ~3UL;
+		}
+		for (int off = STROM_WAVE / 2; off > 0; off >>= 1)
+			sum += (cl_ulong)__shfl_xor((cl_long)sum, off, STROM_WAVE);
+		if ((threadIdx.x & (STROM_WAVE - 1)) == 0 && sum != 0)
+			atomicAdd((unsigned long long *)&totals[r], (unsigned long long)sum);
+	}
+	if (bad)
+		*p_failed = 1;
+}
+
+/* VARLENA: some destination column is text / character(n) (fixed per launch: a mapping of
+ * fixed-width columns runs the code it always ran) */
+template <bool VARLENA>
+static __device__ __forceinline__ void
+gpuhashjoin_projection_column_body(kern_hashjoin *khashjoin,
+								   const kern_multihash *kmhash,
+								   const kern_data_store *kds,
+								   const kern_data_store *ktoast,
+								   kern_data_store *dst,
+								   const cl_int *src_depth,
+								   const cl_int *src_colidx,
+								   cl_uint *col_has_null,		/* [ncols] flags, then one failure flag */
+								   const hashjoin_index *hjidx,
+								   const cl_ulong *dimptr)		/* [2 * ncols] slot-indexed values / isnull arrays, or 0 */
 {
 	/* the mapping and both column directories, staged once: read per (record,
 	 * column) they are dependent scalar loads in front of every gather */
@@ -1895,8 +2075,94 @@ gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
 			const void *addr[HASHJOIN_PROJ_ROWS];
 			cl_long		val[HASHJOIN_PROJ_ROWS];
 			bool		mismatch = false;
+			const bool	is_text = (VARLENA && dstlen < 0);
 
-			if (depth == 0 && s_src_values[r] != 0)
+			if (is_text)
+			{
+				/*
+				 * the datums move to the heap area, their offsets to the column: per turn the wave
+				 * sums its lanes' 4-byte rounded sizes, takes that much from 'usage' with one
+				 * atomic, and each lane copies its datum -- header included, whatever its form --
+				 * to its share (the wave allocator of strom_ingest.h)
+				 */
+				hashjoin_proj_textsrc ts = hashjoin_proj_text_source(kds, kmhash, nrels, depth, col);
+				cl_ulong	heap_off = KERN_DATA_STORE_COLDIR(dst)[r].extra_off;
+				cl_ulong	dst_length = dst->length;
+#pragma unroll
+				for (int k = 0; k < HASHJOIN_PROJ_ROWS; k++)
+				{
+					cl_uint		sz = 0;
+					const char *src = (valid[k]
+									   ? hashjoin_proj_text_datum(ts, kds, ktoast, outer_row[k], rbuf[k], &sz, &mismatch)
+									   : NULL);
+					cl_ulong	room = ((cl_ulong)sz + 3UL) & ~3UL;		/* every datum starts on a 4-byte boundary */
+					cl_ulong	before = room;
+					/* inclusive prefix sum over the wave's lanes */
+#pragma unroll
+					for (int d = 1; d < 64; d <<= 1)
+					{
+						cl_ulong	o = (cl_ulong)__shfl_up((cl_long)before, d, 64);
+						if (lane >= (cl_uint)d)
+							before += o;
+					}
+					cl_ulong	total = (cl_ulong)__shfl((cl_long)before, 63, 64);
+					cl_uint		base_off = 0;
+					if (total > 0 && total <= 0xffffffffUL)
+					{
+						if (lane == 0)
+							base_off = atomicAdd(&dst->usage, (cl_uint)total);
+						base_off = (cl_uint)__shfl((int)base_off, 0, 64);
+					}
+					cl_ulong	at = (cl_ulong)base_off + (before - room);
+					if (src && (at < heap_off || at + room > dst_length))
+					{
+						/* beyond what the sizing pass counted: the two passes disagree */
+						mismatch = true;
+						src = NULL;
+					}
+					if (src)
+					{
+						cl_uint	   *out = (cl_uint *)((char *)dst + at);
+						cl_uint		nwords = (cl_uint)(room >> 2);
+						if (((cl_ulong)src & 3UL) == 0)
+						{
+							/* (a 4-byte header datum is aligned in its tuple) */
+							cl_uint		whole = sz >> 2;
+							for (cl_uint w = 0; w < whole; w++)
+								out[w] = ((const cl_uint *)src)[w];
+							if (whole < nwords)
+							{
+								cl_uint		x = 0;
+								for (cl_uint b = whole << 2; b < sz; b++)
+									x |= (cl_uint)((const cl_uchar *)src)[b] << ((b & 3) * 8);
+								out[whole] = x;		/* zero padded */
+							}
+						}
+						else
+						{
+							for (cl_uint w = 0; w < nwords; w++)
+							{
+								cl_uint		x = 0;
+#pragma unroll
+								for (cl_uint j = 0; j < 4; j++)
+								{
+									cl_uint		b = (w << 2) + j;
+									if (b < sz)
+										x |= (cl_uint)((const cl_uchar *)src)[b] << (j * 8);
+								}
+								out[w] = x;
+							}
+						}
+					}
+					if (valid[k])
+						((cl_ulong *)((char *)dst + s_values_off[r]))[idx[k]] = (src ? at : 0UL);
+					addr[k] = src;
+				}
+				/* (per lane, unlike a width mismatch: one record's datum may be the unreadable one) */
+				if (mismatch)
+					col_has_null[ncols] = 1;
+			}
+			else if (depth == 0 && s_src_values[r] != 0)
 			{
 				/* COLUMN outer chunk: straight from the column array */
 				cl_int	attlen = s_srclen[r];
@@ -1975,7 +2241,7 @@ gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
 			for (int k = 0; k < HASHJOIN_PROJ_ROWS; k++)
 			{
 				val[k] = 0;
-				if (addr[k])
+				if (addr[k] && !is_text)
 				{
 					switch (dstlen)
 					{
@@ -1989,7 +2255,7 @@ gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
 #pragma unroll
 			for (int k = 0; k < HASHJOIN_PROJ_ROWS; k++)
 			{
-				if (valid[k])
+				if (valid[k] && !is_text)
 				{
 					char   *out = (char *)dst + s_values_off[r] + (size_t)dstlen * idx[k];
 					switch (dstlen)
@@ -2022,6 +2288,41 @@ gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
 		if (s_hasnull[r])
 			col_has_null[r] = 1;
 	}
+}
+
+extern "C" __global__ void
+__launch_bounds__(256)
+gpuhashjoin_projection_column(kern_hashjoin *khashjoin,
+							  const kern_multihash *kmhash,
+							  const kern_data_store *kds,
+							  const kern_data_store *ktoast,
+							  kern_data_store *dst,
+							  const cl_int *src_depth,
+							  const cl_int *src_colidx,
+							  cl_uint *col_has_null,
+							  const hashjoin_index *hjidx,
+							  const cl_ulong *dimptr)
+{
+	gpuhashjoin_projection_column_body<false>(khashjoin, kmhash, kds, ktoast, dst, src_depth, src_colidx,
+											  col_has_null, hjidx, dimptr);
+}
+
+/* the second pass over a mapping with text columns (the first: _textsize above) */
+extern "C" __global__ void
+__launch_bounds__(256)
+gpuhashjoin_projection_column_varlena(kern_hashjoin *khashjoin,
+									  const kern_multihash *kmhash,
+									  const kern_data_store *kds,
+									  const kern_data_store *ktoast,
+									  kern_data_store *dst,
+									  const cl_int *src_depth,
+									  const cl_int *src_colidx,
+									  cl_uint *col_has_null,
+									  const hashjoin_index *hjidx,
+									  const cl_ulong *dimptr)
+{
+	gpuhashjoin_projection_column_body<true>(khashjoin, kmhash, kds, ktoast, dst, src_depth, src_colidx,
+											 col_has_null, hjidx, dimptr);
 }
 
 #endif	/* STROM_HASHJOIN_DEVICE_H */

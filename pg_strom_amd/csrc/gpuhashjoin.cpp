@@ -1076,7 +1076,9 @@ strom::hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min,
  * joined rows -> a COLUMN chunk resident in HBM (gpuhashjoin_projection_column
  * in strom_hashjoin.h); zone maps and NULL bookkeeping by the ingest
  * program's kernels, so the result is what strom_dstore_to_column() or a
- * host-built COLUMN chunk would be
+ * host-built COLUMN chunk would be.  Text / character(n) columns: a sizing
+ * kernel first (gpuhashjoin_projection_column_textsize), then the heap area
+ * at its exact size and the projection's _varlena entry point.
  */
 extern "C" strom_dstore *
 strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, strom_dstore *outer,
@@ -1121,10 +1123,31 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	int		errcode = 0;
 	(void)hipSetDevice(dev->hip_id);
 	Program *iprog = lookup_program(ingest_key);
-	hipFunction_t fn_proj = tbl->prog->get_function(dev, "gpuhashjoin_projection_column", &errcode);
+	/* text / character(n) destination columns: their datums go to a heap area behind the column
+	 * arrays, sized by a pass of its own, and the projection carries the heap writer */
+	auto is_text_type = [](int32_t oid) {
+		oid = (oid < 0 ? -oid : oid);
+		return oid == STROM_TEXTOID || oid == STROM_BPCHARNOID;
+	};
+	bool	any_text = false;
+	for (int i = 0; i < ncols; i++)
+	{
+		if (!is_text_type(type_oids[i]))
+			continue;
+		any_text = true;
+		if (src_depth[i] == 0 && outer->head.format == KDS_FORMAT_TUPSLOT)
+		{
+			*p_errcode = StromError_BadRequestMessage;		/* a TUPSLOT chunk holds no datum bytes */
+			return nullptr;
+		}
+	}
+	hipFunction_t fn_proj = tbl->prog->get_function(dev, any_text ? "gpuhashjoin_projection_column_varlena"
+													: "gpuhashjoin_projection_column", &errcode);
+	hipFunction_t fn_size = (fn_proj && any_text)
+		? tbl->prog->get_function(dev, "gpuhashjoin_projection_column_textsize", &errcode) : nullptr;
 	hipFunction_t fn_mm = fn_proj ? iprog->get_function(dev, "ingest_minmax", &errcode) : nullptr;
 	hipFunction_t fn_fin = fn_mm ? iprog->get_function(dev, "ingest_finish", &errcode) : nullptr;
-	if (!fn_proj || !fn_mm || !fn_fin)
+	if (!fn_proj || !fn_mm || !fn_fin || (any_text && !fn_size))
 	{
 		*p_errcode = errcode;
 		return nullptr;
@@ -1147,16 +1170,16 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		switch (type_oids[i] < 0 ? -type_oids[i] : type_oids[i])
 		{
 			case STROM_TEXTOID: case STROM_BPCHARNOID:
-				/* joined rows with text columns leave as heap tuples (the ROW_FLAT projection) */
-				*p_errcode = StromError_BadRequestMessage;
-				return nullptr;
+				/* 8-byte offsets in the column array, the datums in the heap area (strom_kds.h) */
+				attlen = -1;
+				break;
 			case STROM_BOOLOID: case STROM_BPCHAROID:	attlen = 1; break;
 			case STROM_INT2OID:							attlen = 2; break;
 			case STROM_INT4OID: case STROM_FLOAT4OID: case STROM_DATEOID:	attlen = 4; break;
 			default:									attlen = 8; break;
 		}
-		head->colmeta[i].attbyval = 1;
-		head->colmeta[i].attalign = (cl_char)attlen;
+		head->colmeta[i].attbyval = (attlen > 0 ? 1 : 0);
+		head->colmeta[i].attalign = (cl_char)(attlen > 0 ? attlen : 4);
 		head->colmeta[i].attlen = (cl_short)attlen;
 		head->colmeta[i].attnum = (cl_short)(i + 1);
 		head->colmeta[i].attcacheoff = -1;
@@ -1191,7 +1214,8 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	for (int i = 0; use_dim && i < ncols; i++)
 	{
 		void   *vals = nullptr, *nulls = nullptr;
-		if (src_depth[i] == 1 &&
+		/* (fixed-width columns only: a text column always goes through the entry) */
+		if (src_depth[i] == 1 && head->colmeta[i].attlen > 0 &&
 			hashjoin_table_dimcol(tbl, src_colidx[i], head->colmeta[i].attlen, &vals, &nulls) == 0)
 		{
 			dimptr[2 * i] = (cl_ulong)(uintptr_t)vals;
@@ -1201,7 +1225,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	}
 
 	size_t	aux_ints = 4 * (size_t)ncols + 1;		/* depth map, column map, type oids, NULL flags, failure */
-	char   *d_dst = (char *)dev->pool.alloc(off);
+	char   *d_dst = nullptr;						/* (allocated once the heap area's size is known) */
 	cl_int *d_aux = (cl_int *)dev->pool.alloc(sizeof(cl_int) * aux_ints);
 	cl_ulong *d_dimptr = (cl_ulong *)dev->pool.alloc(sizeof(cl_ulong) * dimptr.size());
 	std::vector<cl_int> aux(aux_ints, 0);
@@ -1211,19 +1235,29 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	bool	any_zone_map = false;
 	for (int i = 0; i < ncols; i++)
 	{
-		aux[2 * ncols + i] = (type_oids[i] > 0 ? type_oids[i] : 0);
-		any_zone_map = any_zone_map || (type_oids[i] > 0);
+		/* (a text column never has a zone map) */
+		bool	zm = (type_oids[i] > 0 && !is_text_type(type_oids[i]));
+		aux[2 * ncols + i] = (zm ? type_oids[i] : 0);
+		any_zone_map = any_zone_map || zm;
 	}
 	hipStream_t stream = dev->streams[0];
 	strom_dstore *result = nullptr;
+	char   *d_size = nullptr;						/* sizing pass: totals[ncols], then attlen[ncols] */
+	/* STROM_HASHJOIN_PROJECT_TIMING: HIP-event times of the two kernels on stderr (the probe's switch) */
+	hipEvent_t	ev[4] = { nullptr, nullptr, nullptr, nullptr };
+	bool		timing = (getenv("STROM_HASHJOIN_PROJECT_TIMING") != nullptr);
+	for (int i = 0; timing && i < 4; i++)
+		timing = (hipEventCreate(&ev[i]) == hipSuccess);
+	/* (the projection takes 4 records per thread and turn: HASHJOIN_PROJ_ROWS) */
+	unsigned	pgrid = (unsigned)std::min<size_t>(((size_t)nitems + 1023) / 1024,
+												   (size_t)dev->prop.multiProcessorCount * 8);
 	do {
-		if (!d_dst || !d_aux || !d_dimptr)
+		if (!d_aux || !d_dimptr)
 		{
 			*p_errcode = StromError_OutOfMemory;
 			break;
 		}
-		if (hipMemcpyAsync(d_dst, hbuf.data(), hbuf.size(), hipMemcpyHostToDevice, stream) != hipSuccess ||
-			hipMemcpyAsync(d_dimptr, dimptr.data(), sizeof(cl_ulong) * dimptr.size(),
+		if (hipMemcpyAsync(d_dimptr, dimptr.data(), sizeof(cl_ulong) * dimptr.size(),
 						   hipMemcpyHostToDevice, stream) != hipSuccess ||
 			hipMemcpyAsync(d_aux, aux.data(), sizeof(cl_int) * aux_ints, hipMemcpyHostToDevice, stream) != hipSuccess)
 		{
@@ -1234,6 +1268,89 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		const void *a_km = tbl->d_kmhash;
 		const void *a_kds = outer->devptr;
 		const void *a_toast = nullptr;
+		if (any_text)
+		{
+			/*
+			 * the heap area behind the column arrays, at its exact size: an inner datum is repeated
+			 * once per joined row, so the sources' lengths bound nothing; the sizing kernel adds up
+			 * what the projection will copy.  'usage' is the writer's cursor, as in ingest.cpp.
+			 */
+			size_t		size_len = (sizeof(cl_ulong) + sizeof(cl_int)) * (size_t)ncols;
+			std::vector<char> sbuf(size_len, 0);
+			cl_ulong   *totals = (cl_ulong *)sbuf.data();
+			cl_int	   *attlens = (cl_int *)(sbuf.data() + sizeof(cl_ulong) * (size_t)ncols);
+			cl_int		failed = 0;
+			for (int i = 0; i < ncols; i++)
+				attlens[i] = head->colmeta[i].attlen;
+			if (pgrid > 0)
+			{
+				d_size = (char *)dev->pool.alloc(size_len);
+				if (!d_size)
+				{
+					*p_errcode = StromError_OutOfMemory;
+					break;
+				}
+				const void *a_md = d_aux;
+				const void *a_mc = d_aux + ncols;
+				const void *a_len = d_size + sizeof(cl_ulong) * (size_t)ncols;
+				void	   *a_tot = d_size;
+				void	   *a_fail = d_aux + 4 * (size_t)ncols;
+				cl_uint		a_nitems = nitems;
+				cl_uint		a_ncols = (cl_uint)ncols;
+				void	   *args_size[] = { &a_khj, &a_km, &a_kds, &a_toast, &a_nitems, &a_ncols, &a_md, &a_mc,
+											&a_len, &a_tot, &a_fail };
+				if (hipMemcpyAsync(d_size, sbuf.data(), size_len, hipMemcpyHostToDevice, stream) != hipSuccess ||
+					(timing && hipEventRecord(ev[0], stream) != hipSuccess) ||
+					hipModuleLaunchKernel(fn_size, pgrid, 1, 1, 256, 1, 1, 0, stream, args_size, nullptr) != hipSuccess ||
+					(timing && hipEventRecord(ev[1], stream) != hipSuccess) ||
+					hipMemcpyAsync(sbuf.data(), d_size, sizeof(cl_ulong) * (size_t)ncols,
+								   hipMemcpyDeviceToHost, stream) != hipSuccess ||
+					hipMemcpyAsync(&failed, d_aux + 4 * (size_t)ncols, sizeof(cl_int),
+								   hipMemcpyDeviceToHost, stream) != hipSuccess ||
+					hipStreamSynchronize(stream) != hipSuccess)
+				{
+					*p_errcode = StromError_HipInternal;
+					break;
+				}
+			}
+			if (failed)
+			{
+				/* a text destination on a fixed-width source, or a datum beyond its chunk */
+				*p_errcode = StromError_DataStoreCorruption;
+				break;
+			}
+			uint64_t	heap_off = off;
+			uint64_t	heap_len = 0;
+			bool		fits = true;
+			for (int i = 0; i < ncols && fits; i++)
+			{
+				fits = (totals[i] <= 0xffffffffUL);
+				heap_len += totals[i];
+			}
+			uint64_t	total_len = STROM_TYPEALIGN(KDS_COLUMN_ALIGN, heap_off + heap_len);
+			if (!fits || total_len > 0xffffffffUL)
+			{
+				*p_errcode = StromError_DataStoreOutOfRange;
+				break;
+			}
+			for (int i = 0; i < ncols; i++)
+				if (head->colmeta[i].attlen < 0)
+					cd[i].extra_off = (cl_uint)heap_off;
+			off = (size_t)total_len;
+			head->length = (cl_uint)off;
+			head->usage = (cl_uint)heap_off;
+		}
+		d_dst = (char *)dev->pool.alloc(off);
+		if (!d_dst)
+		{
+			*p_errcode = StromError_OutOfMemory;
+			break;
+		}
+		if (hipMemcpyAsync(d_dst, hbuf.data(), hbuf.size(), hipMemcpyHostToDevice, stream) != hipSuccess)
+		{
+			*p_errcode = StromError_HipInternal;
+			break;
+		}
 		void	   *a_dst = d_dst;
 		const void *a_md = d_aux;
 		const void *a_mc = d_aux + ncols;
@@ -1246,11 +1363,10 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		void	   *args_fin[] = { &a_dst, &a_oids, &a_flags };
 		unsigned	grid = (unsigned)std::min<size_t>(((size_t)nitems + 255) / 256,
 													  (size_t)dev->prop.multiProcessorCount * 8);
-		/* (the projection takes 4 records per thread and turn: HASHJOIN_PROJ_ROWS) */
-		unsigned	pgrid = (unsigned)std::min<size_t>(((size_t)nitems + 1023) / 1024,
-													   (size_t)dev->prop.multiProcessorCount * 8);
 		if (grid > 0 &&
-			(hipModuleLaunchKernel(fn_proj, pgrid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) != hipSuccess ||
+			((timing && hipEventRecord(ev[2], stream) != hipSuccess) ||
+			 hipModuleLaunchKernel(fn_proj, pgrid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) != hipSuccess ||
+			 (timing && hipEventRecord(ev[3], stream) != hipSuccess) ||
 			 (any_zone_map &&
 			  hipModuleLaunchKernel(fn_mm, std::min(grid, (unsigned)dev->prop.multiProcessorCount),
 									(unsigned)ncols, 1, 256, 1, 1, 0, stream, args_mm, nullptr) != hipSuccess)))
@@ -1276,16 +1392,29 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 			*p_errcode = StromError_HipInternal;
 			break;
 		}
+		if (timing && grid > 0)
+		{
+			float	ms_size = 0, ms_proj = 0;
+			if (any_text)
+				(void)hipEventElapsedTime(&ms_size, ev[0], ev[1]);
+			(void)hipEventElapsedTime(&ms_proj, ev[2], ev[3]);
+			fprintf(stderr, "strom_hashjoin_project_column: %u rows, textsize %.3f ms, projection %.3f ms\n",
+					nitems, ms_size, ms_proj);
+		}
 		if (failed)
 		{
-			/* a mapped source column is not as wide as its destination type */
+			/* a mapped source column is not as wide as its destination type (or, for a text
+			 * column, the projection met a datum the sizing pass did not count) */
 			delete result;
 			result = nullptr;
 			*p_errcode = StromError_DataStoreCorruption;
 			break;
 		}
 	} while (0);
+	for (int i = 0; i < 4; i++)
+		if (ev[i]) (void)hipEventDestroy(ev[i]);
 	if (d_aux) dev->pool.release(d_aux);
+	if (d_size) dev->pool.release(d_size);
 	if (d_dimptr) dev->pool.release(d_dimptr);
 	if (!result && d_dst) dev->pool.release(d_dst);
 	return result;

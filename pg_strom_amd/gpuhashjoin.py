@@ -304,12 +304,15 @@ class GpuHashJoin(object):
         """join a RESIDENT chunk and leave the joined rows in HBM as a COLUMN chunk
         for the next operator (strom_hashjoin_project_column): dest_columns as in
         join_chunk_project.  Returns (DeviceStore, nitems); the result pairs never
-        cross PCIe.  zone_maps=False when the consumer brings its own key domain."""
-        from .kds import SQL_TYPES
+        cross PCIe.  zone_maps=False when the consumer brings its own key domain.
+        "text" / "character" columns keep their datums in the result's heap area
+        (kds.decode_text_column reads them back from a download)."""
+        from .kds import column_type_oid
         ncols = len(dest_columns)
         depth = np.array([d for d, _, _ in dest_columns], dtype=np.int32)
         colidx = np.array([a - 1 for _, a, _ in dest_columns], dtype=np.int32)
-        oids = np.array([SQL_TYPES[t][0] for _, _, t in dest_columns], dtype=np.int32)
+        # (a varlena type is named by its own tag: pg_type's 1042 alone is the by-value char(1))
+        oids = np.array([column_type_oid(t) for _, _, t in dest_columns], dtype=np.int32)
         if not zone_maps:
             oids = -oids                                     # widths only: no min/max pass
         for attempt in range(2):

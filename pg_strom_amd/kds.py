@@ -55,6 +55,15 @@ SQL_TYPES = {
 
 VARLENA_RAW_TYPES = ("numeric_raw", "text", "character", "text_raw")
 
+STROM_BPCHARNOID = 0x10000 | 1042      # character(n) as a varlena (strom_kds.h); 1042 alone: char(1)
+
+
+def column_type_oid(sqltype):
+    """the type tag of a COLUMN chunk's column for the C ABI: character(n) kept as a varlena
+    has a tag of its own, every other type its pg_type oid"""
+    oid, attlen, _ = SQL_TYPES[sqltype]
+    return STROM_BPCHARNOID if (oid == 1042 and attlen < 0) else oid
+
 
 def varlena_datum(payload):
     """payload bytes -> the varlena datum PostgreSQL would store (short header when it fits)"""
@@ -310,6 +319,34 @@ def decode_column_chunk(buf):
         out.append(dict(values=vals, notnull=notnull, stat_flags=int(cd[c]["stat_flags"]),
                         minval=int(cd[c]["minval"]), maxval=int(cd[c]["maxval"]),
                         extra_off=int(cd[c]["extra_off"])))
+    return out
+
+
+def decode_text_column(buf, col):
+    """one text / character(n) column of a KDS_FORMAT_COLUMN image -> the payload of every row
+    (bytes, None for NULL): the row's offset, the datum's header there, then the payload.
+    A compressed or external datum comes back whole, header included, as a bytearray."""
+    head = KdsHead(buf)
+    c = decode_column_chunk(buf)[col]
+    assert int(head.colmeta[col]["attlen"]) < 0
+    offs = c["values"].view(np.uint64)
+    out = []
+    for i in range(head.nitems):
+        at = int(offs[i])
+        if at == 0 or (c["notnull"] is not None and not c["notnull"][i]):
+            out.append(None)
+            continue
+        b0 = int(buf[at])
+        if b0 == 0x01:                                      # external TOAST pointer
+            out.append(bytearray(buf[at:at + 2 + (16 if int(buf[at + 1]) == 18 else 8)].tobytes()))
+        elif b0 & 1:
+            out.append(buf[at + 1:at + ((b0 >> 1) & 0x7f)].tobytes())
+        else:
+            word = int(np.frombuffer(buf[at:at + 4].tobytes(), dtype="<u4")[0])
+            if word & 3:                                    # compressed
+                out.append(bytearray(buf[at:at + (word >> 2)].tobytes()))
+            else:
+                out.append(buf[at + 4:at + (word >> 2)].tobytes())
     return out
 
 

@@ -47,7 +47,8 @@
 #define GPUPREAGG_QUADS		2
 #endif
 #define GPUPREAGG_TILE_ROWS	(GPUPREAGG_BLOCK * 4 * GPUPREAGG_QUADS)
-#define GPUPREAGG_MAXKEYS	8
+
+#include "strom_ctl.h"		/* the control blocks the host writes, the bounds of their arrays */
 
 struct strom_kparams {
 #define X(idx,NAME)	pg_##NAME##_t KPARAM_##idx;
@@ -108,25 +109,6 @@ GPUPREAGG_KEY_LIST(X)
 	gpupreagg_agg_##aidx(cl_int *errcode, const strom_kparams &KP, const strom_kvars &KV);
 GPUPREAGG_AGG_LIST(X)
 #undef X
-
-/* control block written by the host (gpupreagg.cpp mirrors this struct) */
-struct gpupreagg_dense_ctl {
-	cl_uint		ngroups;			/* dense ids in the whole domain */
-	cl_uint		nsplits;			/* work-group roles over the id range */
-	cl_uint		groups_per_split;
-	cl_uint		nrep;				/* LDS replicas, power of two */
-	cl_uint		nslabs;				/* == gridDim.x */
-	cl_uint		nkeys;
-	cl_ulong	slab_bytes;
-	cl_long		key_min[GPUPREAGG_MAXKEYS];
-	cl_uint		key_range[GPUPREAGG_MAXKEYS];	/* max-min+1; NULL slot == key_range */
-	cl_uint		key_stride[GPUPREAGG_MAXKEYS];
-	/* compaction (strom_gpupreagg_compact): dense id -> slot of the ids that
-	 * actually occur, ~0 = absent; 0 = ids are used as they are */
-	cl_ulong	remap;				/* device address of cl_uint[dense_ngroups] */
-	cl_uint		dense_ngroups;		/* product of (key_range + 1) */
-	cl_uint		merge_ws;			/* stripes of the slab merge (power of two <= 64), 0 = derive */
-};
 
 /*
  * dense id -> table slot; false when the combination is not in the table.
@@ -230,12 +212,8 @@ gpupreagg_numeric_combine(cl_ulong acc, cl_ulong v, cl_int *errcode)
 
 STROM_DEVICE cl_uint gpupreagg_align16(cl_uint v) { return (v + 15u) & ~15u; }
 
-/*
- * Per-group flags: bit 0 = a row of this group passed the qual ("seen"),
- * bit 1+a = aggregate a received a non-NULL input.  One word per (group,
- * replica) so that a row updates all its flags with ONE LDS operation, and
- * after the first row of a group only a read remains.
- */
+/* per-group flags (strom_ctl.h: gpupreagg_flag_width), updated by a row with ONE LDS operation; after
+ * the first row of a group only a read remains */
 #if GPUPREAGG_NAGGS <= 7
 typedef cl_uchar	gpupreagg_flags_t;
 #elif GPUPREAGG_NAGGS <= 15
@@ -243,52 +221,17 @@ typedef cl_ushort	gpupreagg_flags_t;
 #else
 typedef cl_uint		gpupreagg_flags_t;
 #endif
+static_assert(sizeof(gpupreagg_flags_t) == gpupreagg_flag_width(GPUPREAGG_NAGGS), "flag width");
 #define GPUPREAGG_FLAG_SEEN		1u
 
-/*
- * LDS / slab image for G groups and REP replicas:
- *   section 0        flags[G*REP]
- *   section 1+a      values of aggregate a: u32[G*REP] (NROWS) or 8 bytes[G*REP]
- *   section 1+NAGGS  total size
- * 32-bit offsets: the image lives in LDS (<= 160 KB) or in a slab of the
- * same shape.
- */
+/* the LDS / slab image of this program's aggregates (strom_ctl.h: gpupreagg_image_offset_of; the
+ * resident table's gpupreagg_table_offset is there too) */
 STROM_DEVICE cl_uint
 gpupreagg_image_offset(int sec, cl_uint G, cl_uint REP)
 {
-	cl_uint	off = 0;
-	int		cur = 0;
-
-	if (sec == cur) return off;
-	off += gpupreagg_align16((cl_uint)sizeof(gpupreagg_flags_t) * G * REP); cur++;
-#define X(aidx,resno,OP,NAME)																\
-	if (sec == cur) return off;																\
-	off += gpupreagg_align16((GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS ? 4u : 8u) * G * REP);	\
-	cur++;
-	GPUPREAGG_AGG_LIST(X)
+#define X(aidx,resno,OP,NAME)	| (GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS ? 1u << (aidx) : 0u)
+	return gpupreagg_image_offset_of<cl_uint>(sec, G, REP, GPUPREAGG_NAGGS, 0u GPUPREAGG_AGG_LIST(X));
 #undef X
-	return off;
-}
-
-/*
- * resident table for N groups, 256-byte aligned sections:
- *   section 0          flags as u32[N]
- *   section 1+a        8-byte values[N] (NROWS widened to i64)
- *   section 1+NAGGS+j  the j-th INTEGER sum's high word, i64[N]: such a sum is
- *                      128 bits wide in the table (low word in its section 1+a,
- *                      two's complement), so a total over any number of chunks
- *                      cannot wrap ("integer sums never wrap", below)
- */
-STROM_DEVICE size_t
-gpupreagg_table_offset(int sec, cl_uint N)
-{
-	size_t	off = 0;
-	size_t	flags = STROM_TYPEALIGN(256, sizeof(cl_uint) * (size_t)N);
-	size_t	vals = STROM_TYPEALIGN(256, 8 * (size_t)N);
-
-	if (sec == 0) return off;
-	off += flags;
-	return off + vals * (size_t)(sec - 1);
 }
 
 /*
@@ -498,19 +441,7 @@ gpupreagg_sum_magnitude(cl_long v)
 	return (cl_ulong)(v ^ (v >> 63));
 }
 
-/*
- * what the range proof reads, in the 8 padding bytes of kern_gpupreagg (written by
- * the host per request): the bit count B of the largest input magnitude -- preset with
- * what is known statically, raised by the folds (atomic max) -- and the rows ONE
- * work-group folds at most; sortbuf_len -- the reference's sort buffer length, no use
- * here -- carries the rows of the whole request
- */
-#define KERN_GPUPREAGG_SUM_MAGBITS(kgp)		((cl_uint *)((kgp)->__padding))
-#define KERN_GPUPREAGG_WG_ROWS(kgp)			(*(const cl_uint *)((kgp)->__padding + 4) & 0x7fffffffu)
-/* top bit of that word: the host has bounded the sums of PLAIN columns (GPUPREAGG_SUMBITS_<a> 65) and
- * of expressions over decimal columns (66: GPUPREAGG_SUMBOUND_<a>, a formula over the columns' zone
- * maps from the code generator) by the chunk's zone maps -- the fold need not measure them */
-#define KERN_GPUPREAGG_ZONE_BOUNDED(kgp)	((*(const cl_uint *)((kgp)->__padding + 4) >> 31) != 0)
+/* (what the range proof reads per request, KERN_GPUPREAGG_SUM_MAGBITS / _WG_ROWS / _ZONE_BOUNDED / _FOLD_NROWS: strom_ctl.h) */
 /*
  * per-launch facts the row functions take as one word:
  *   ROWFLAG_ZONE_BOUNDED   see above
@@ -529,7 +460,6 @@ gpupreagg_sum_magnitude(cl_long v)
 	 ((GPUPREAGG_SUMBITS_##aidx == 65 || GPUPREAGG_SUMBITS_##aidx == 66) && !((rowflags) & ROWFLAG_ZONE_BOUNDED)))
 #define GPUPREAGG_COUNT_IS_ALIASED(aidx, rowflags)	\
 	(GPUPREAGG_COUNTALL_##aidx && (aidx) != GPUPREAGG_COUNTALL_FIRST && ((rowflags) & ROWFLAG_ALL_NOTNULL))
-#define KERN_GPUPREAGG_FOLD_NROWS(kgp)		((cl_uint)(kgp)->sortbuf_len)
 
 STROM_DEVICE void
 gpupreagg_writeback_summag(kern_gpupreagg *kgpreagg, cl_ulong summag)
@@ -977,18 +907,6 @@ gpupreagg_writeback_status(cl_int *status, cl_int chunk_status)
  * and NULL-free columns allow it, the fields fit 64 bits and the packed image
  * needs fewer roles than the standard one.
  * ---------------------------------------------------------------------- */
-#define GPUPREAGG_PACK_MAXAGGS	32
-struct gpupreagg_pack_ctl {
-	cl_uint		count_shift;					/* count field: bits count_shift .. 63 */
-	cl_uint		nwords;							/* 1 (the packed word) + float8 sums */
-	cl_uint		spill_at;						/* 0, or: a group whose count field reaches this moves to the slab */
-	cl_uint		count_limit;					/* spill_at != 0: the count field's largest value */
-	cl_uint		shift[GPUPREAGG_PACK_MAXAGGS];	/* kind 2: position of the field in word 0 */
-	cl_uint		word[GPUPREAGG_PACK_MAXAGGS];	/* kind 3: the aggregate's own word */
-	cl_ulong	mask[GPUPREAGG_PACK_MAXAGGS];	/* kind 2: field mask (after the shift) */
-	cl_ulong	vmax[GPUPREAGG_PACK_MAXAGGS];	/* kind 2: max - min of the column (zone map) */
-	cl_long		bias[GPUPREAGG_PACK_MAXAGGS];	/* kind 2: min of the column */
-};
 
 #if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
 STROM_DEVICE cl_uint
@@ -1448,30 +1366,6 @@ gpupreagg_dense_generic(kern_gpupreagg *kgpreagg,
  * (hashjoin_build_dimcol_kernel) at slot = outer key - key_min.  The
  * program's (var N ...) are the virtual relation's columns.
  * ====================================================================== */
-struct gpupreagg_joined_map {
-	cl_uint		ncols;
-	cl_int		key_col;			/* outer column (0-based) that is the join key */
-	cl_int		key_attlen;
-	cl_uint		nslots;
-	cl_long		key_min;
-	struct {
-		cl_int		depth;
-		cl_int		col;
-		cl_ulong	dimvalues;		/* depth 1: device arrays by slot */
-		cl_ulong	dimisnull;
-	} c[64];
-	/* gpupreagg_dense_lookup: packed slot records (hashjoin_build_dimrec_kernel); an inner
-	 * column i then has c[i].dimvalues = byte offset of its value in the record and
-	 * c[i].dimisnull = its bit in the record's flags word */
-	cl_ulong	recs;
-	cl_uint		reclen;
-	/* NARROW records (hashjoin_dimrec_narrow_kernel, lookup only): reclen 2 or 4, the word is
-	 * presence | NULL bits | (value - nmin) fields; inner column i = nmin[i] + field */
-	cl_uint		narrow;
-	cl_uint		nshift[64];
-	cl_uint		nmask[64];
-	cl_long		nmin[64];
-};
 
 #if !defined(GPUPREAGG_LOOKUP_ONLY)
 extern "C" __global__ void
@@ -2526,16 +2420,8 @@ gpupreagg_reg1_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
  * keys -- goes through an open-addressing table in HBM keyed by the keys'
  * canonical 64-bit images (the reference sorts row indexes by
  * gpupreagg_keycomp instead, opencl_gpupreagg.h:620-856).  One slot is one
- * record, so a probe touches one cache line:
- *
- *   +0   state  u32     0 empty, 1 being claimed, 2 ready
- *   +4   knull  u32     bit k: key k is NULL
- *   +8   flags  u32     bit 0 seen, bit 1+a aggregate a has a value
- *   +16  keys[NKEYS]    u64 images
- *        vals[NAGGS]    8 bytes each (NROWS widened to i64, float min/max as
- *                       order-preserving keys, like the dense table)
- *
- * records start GPUPREAGG_HASH_HEAD bytes into the table, after the head.
+ * record, so a probe touches one cache line; the head and the record layout
+ * are in strom_ctl.h (the host sizes, initialises and reads the table).
  *
  * A chunk is folded in two launches: gpupreagg_hash_check evaluates every
  * row for errors only; gpupreagg_hash_fold runs if the chunk is clean, so a
@@ -2545,16 +2431,11 @@ gpupreagg_reg1_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
  * reach HBM once per work-group, the others go to the global table row by
  * row.
  * ====================================================================== */
-#define GPUPREAGG_HASH_HEAD		256
-#define GPUPREAGG_HASH_RECLEN	(16 + 8 * (GPUPREAGG_NKEYS + GPUPREAGG_NAGGS))
-#define GPUPREAGG_HASH_STRIDE	(GPUPREAGG_HASH_RECLEN <= 32 ? 32 :					\
-								 GPUPREAGG_HASH_RECLEN <= 64 ? 64 :					\
-								 ((GPUPREAGG_HASH_RECLEN + 127) / 128 * 128))
+#define GPUPREAGG_HASH_RECLEN	GPUPREAGG_HASH_RECLEN_OF(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS)
+#define GPUPREAGG_HASH_STRIDE	GPUPREAGG_HASH_STRIDE_OF(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS)
 #ifndef GPUPREAGG_HASH_UNROLL
 #define GPUPREAGG_HASH_UNROLL	2		/* 4 needs 66 VGPRs: the second work-group of a CU no longer fits */
 #endif
-/* queued row numbers per wave (roles): a power of two, >= 64 * (UNROLL + 1) */
-#define GPUPREAGG_HASH_QUEUE	256
 /* role map (one byte per row, written by the check pass): low 6 bits = the row's role among
  * up to 64; this value = no role folds the row (the qual dropped it, or padding) */
 #define GPUPREAGG_ROLE_NONE		0xffu
@@ -2566,27 +2447,6 @@ gpupreagg_reg1_column(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 static_assert(GPUPREAGG_HASH_QUEUE >= 64 * (GPUPREAGG_HASH_UNROLL + 1) &&
 			  (GPUPREAGG_HASH_QUEUE & (GPUPREAGG_HASH_QUEUE - 1)) == 0, "role queue too small for the tile");
 
-struct gpupreagg_hash_head {
-	cl_uint		capacity;			/* power of two */
-	cl_uint		nkeys;
-	cl_uint		ngroups;			/* slots claimed so far */
-	cl_uint		overflow;			/* set when a probe found no free slot */
-	cl_uint		stride;				/* GPUPREAGG_HASH_STRIDE, checked by the host */
-	cl_uint		naggs;
-	cl_uint		__pad[2];
-	/*
-	 * integer sums never wrap ("integer sums never wrap", above -- here for a table whose
-	 * accumulators are 64 bits wide and are updated by atomics all over the chip): an upper
-	 * bound of |any partial sum in this table|, the sum over the folded chunks of
-	 * rows x 2^(bits of the largest input magnitude).  While it stays below 2^63 nothing can have
-	 * wrapped and nothing is checked.  Two slots: the fold of turn k reads slot k & 1 and
-	 * (its first work-group) writes the other, which the fold of turn k + 1 reads -- no
-	 * work-group of a launch reads what another one of it writes.  The host counts a turn
-	 * where it queues the first launch of a request's fold, and every such launch writes
-	 * the other slot, whether it folds (gpupreagg_hash_sum_account) or not (.._sum_carry).
-	 */
-	cl_ulong	sum_bound[2];
-};
 
 /*
  * a fold is about to add the request's rows to the table: is the bound still below
@@ -2639,11 +2499,7 @@ STROM_DEVICE char *gpupreagg_hash_rec(char *htab, cl_uint slot)
 { return htab + GPUPREAGG_HASH_HEAD + (size_t)slot * GPUPREAGG_HASH_STRIDE; }
 STROM_DEVICE const char *gpupreagg_hash_rec(const char *htab, cl_uint slot)
 { return htab + GPUPREAGG_HASH_HEAD + (size_t)slot * GPUPREAGG_HASH_STRIDE; }
-#define HASH_REC_STATE(rec)		((cl_uint *)(rec))
-#define HASH_REC_KNULL(rec)		((cl_uint *)((rec) + 4))
-#define HASH_REC_FLAGS(rec)		((cl_uint *)((rec) + 8))
-#define HASH_REC_KEYS(rec)		((cl_ulong *)((rec) + 16))
-#define HASH_REC_VALS(rec)		((cl_ulong *)((rec) + 16) + GPUPREAGG_NKEYS)
+#define HASH_REC_VALS(rec)		(HASH_REC_KEYS(rec) + GPUPREAGG_NKEYS)
 
 STROM_DEVICE cl_ulong strom_key_image(cl_char v)	{ return (cl_ulong)(cl_long)v; }
 STROM_DEVICE cl_ulong strom_key_image(cl_short v)	{ return (cl_ulong)(cl_long)v; }
@@ -3319,16 +3175,6 @@ gpupreagg_hash_fold(kern_gpupreagg *kgpreagg, const kern_data_store *kds,
 #define GPUPREAGG_PART_MAX			4096
 #define GPUPREAGG_SCATTER_ROWS		32		/* rows per thread and tile of the scatter */
 
-struct gpupreagg_part_ctl {
-	cl_uint		nparts;				/* power of two, <= GPUPREAGG_PART_MAX */
-	cl_uint		pshift;
-	cl_uint		unit_rows;
-	cl_uint		nunits;				/* by gpupreagg_hash_part_plan */
-	cl_uint		nrecords;
-	cl_uint		deferred;			/* by the claim pass */
-	cl_uint		max_units;
-	cl_uint		reclen;				/* the host's record length (it sized the buffer): checked by the kernels */
-};
 
 /* the scatter and the fold: do host and device mean the same record?  (a mismatch would write
  * past the buffer) */
@@ -4174,7 +4020,7 @@ gpupreagg_hash_init(char *htab)
 }
 
 /*
- * the groups, packed for the host: records of
+ * the groups, packed for the host: records of gpupreagg_export_rec
  * { knull u32, flags u32, keys[NKEYS] u64, vals[NAGGS] u64 } in out[], their
  * number in *counter (the order is arbitrary: partial rows are a set)
  */
@@ -4183,7 +4029,7 @@ __launch_bounds__(256)
 gpupreagg_hash_export(const char *htab, char *out, cl_uint *counter)
 {
 	const gpupreagg_hash_head *head = (const gpupreagg_hash_head *)htab;
-	const size_t	reclen = 8 + 8 * (GPUPREAGG_NKEYS + GPUPREAGG_NAGGS);
+	const size_t	reclen = GPUPREAGG_EXPORT_RECLEN(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS);
 	cl_uint		C = head->capacity;
 
 	for (cl_uint base = blockIdx.x * blockDim.x; base < C; base += gridDim.x * blockDim.x)
@@ -4203,9 +4049,9 @@ gpupreagg_hash_export(const char *htab, char *out, cl_uint *counter)
 			continue;
 		cl_uint		idx = first + (cl_uint)__popcll(mask & ((1UL << strom_lane_id()) - 1));
 		char	   *rec = out + reclen * idx;
-		((cl_uint *)rec)[0] = *HASH_REC_KNULL(src);
-		((cl_uint *)rec)[1] = *HASH_REC_FLAGS(src);
-		cl_ulong   *body = (cl_ulong *)(rec + 8);
+		((gpupreagg_export_rec *)rec)->knull = *HASH_REC_KNULL(src);
+		((gpupreagg_export_rec *)rec)->flags = *HASH_REC_FLAGS(src);
+		cl_ulong   *body = ((gpupreagg_export_rec *)rec)->body;
 		for (int k = 0; k < GPUPREAGG_NKEYS + GPUPREAGG_NAGGS; k++)
 			body[k] = HASH_REC_KEYS(src)[k];
 	}
@@ -4267,7 +4113,7 @@ gpupreagg_hash_export_parts(const char *htab, char *out, cl_uint nparts,
 							const cl_uint *offsets, cl_uint *cursors)
 {
 	const gpupreagg_hash_head *head = (const gpupreagg_hash_head *)htab;
-	const size_t	reclen = 8 + 8 * (GPUPREAGG_NKEYS + GPUPREAGG_NAGGS);
+	const size_t	reclen = GPUPREAGG_EXPORT_RECLEN(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS);
 	cl_uint		C = head->capacity;
 
 	for (cl_uint base = blockIdx.x * blockDim.x; base < C; base += gridDim.x * blockDim.x)
@@ -4294,9 +4140,9 @@ gpupreagg_hash_export_parts(const char *htab, char *out, cl_uint nparts,
 		if (!ready)
 			continue;
 		char	   *rec = out + reclen * idx;
-		((cl_uint *)rec)[0] = *HASH_REC_KNULL(src);
-		((cl_uint *)rec)[1] = *HASH_REC_FLAGS(src);
-		cl_ulong   *body = (cl_ulong *)(rec + 8);
+		((gpupreagg_export_rec *)rec)->knull = *HASH_REC_KNULL(src);
+		((gpupreagg_export_rec *)rec)->flags = *HASH_REC_FLAGS(src);
+		cl_ulong   *body = ((gpupreagg_export_rec *)rec)->body;
 		for (int k = 0; k < GPUPREAGG_NKEYS + GPUPREAGG_NAGGS; k++)
 			body[k] = HASH_REC_KEYS(src)[k];
 	}
@@ -4383,7 +4229,7 @@ gpupreagg_hash_import(char *htab, const char *recs, cl_uint seg_len, cl_uint nse
 					  const cl_uint *counts, cl_uint skip_seg)
 {
 	gpupreagg_hash_head *head = (gpupreagg_hash_head *)htab;
-	const size_t	reclen = 8 + 8 * (GPUPREAGG_NKEYS + GPUPREAGG_NAGGS);
+	const size_t	reclen = GPUPREAGG_EXPORT_RECLEN(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS);
 	size_t		total = (size_t)seg_len * nsegs;
 
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
@@ -4393,9 +4239,9 @@ gpupreagg_hash_import(char *htab, const char *recs, cl_uint seg_len, cl_uint nse
 		if (seg == skip_seg || j >= counts[seg])
 			continue;
 		const char *rec = recs + reclen * i;
-		cl_uint		knull = ((const cl_uint *)rec)[0];
-		cl_uint		flags = ((const cl_uint *)rec)[1];
-		const cl_ulong *body = (const cl_ulong *)(rec + 8);
+		cl_uint		knull = ((const gpupreagg_export_rec *)rec)->knull;
+		cl_uint		flags = ((const gpupreagg_export_rec *)rec)->flags;
+		const cl_ulong *body = ((const gpupreagg_export_rec *)rec)->body;
 		cl_ulong	kimg[GPUPREAGG_NKEYS + 1];
 		for (int k = 0; k < GPUPREAGG_NKEYS; k++)
 			kimg[k] = body[k];
@@ -4433,14 +4279,14 @@ extern "C" __global__ void
 __launch_bounds__(256)
 gpupreagg_hash_import_verify(char *htab, const char *recs, cl_uint count, cl_uint *overflowed)
 {
-	const size_t	reclen = 8 + 8 * (GPUPREAGG_NKEYS + GPUPREAGG_NAGGS);
+	const size_t	reclen = GPUPREAGG_EXPORT_RECLEN(GPUPREAGG_NKEYS, GPUPREAGG_NAGGS);
 
 	for (cl_uint i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x)
 	{
 		const char *rec = recs + reclen * i;
-		cl_uint		knull = ((const cl_uint *)rec)[0];
-		cl_uint		flags = ((const cl_uint *)rec)[1];
-		const cl_ulong *body = (const cl_ulong *)(rec + 8);
+		cl_uint		knull = ((const gpupreagg_export_rec *)rec)->knull;
+		cl_uint		flags = ((const gpupreagg_export_rec *)rec)->flags;
+		const cl_ulong *body = ((const gpupreagg_export_rec *)rec)->body;
 		cl_ulong	kimg[GPUPREAGG_NKEYS + 1];
 		for (int k = 0; k < GPUPREAGG_NKEYS; k++)
 			kimg[k] = body[k];
@@ -4645,13 +4491,6 @@ gpupreagg_census(const kern_gpupreagg *kgpreagg, const kern_data_store *kds,
  * key; a lane keeps its own pair, a wave combines by shuffles, one atomic
  * pair per wave and key.
  * ====================================================================== */
-struct gpupreagg_keyrange_t {
-	cl_long		kmin[GPUPREAGG_MAXKEYS];
-	cl_long		kmax[GPUPREAGG_MAXKEYS];
-	cl_uint		nvalues[GPUPREAGG_MAXKEYS];		/* != 0: the key had a non-NULL value */
-	cl_uint		nrows;							/* != 0: a row passed the qual */
-	cl_uint		__pad;
-};
 
 template <bool IS_COLUMN>
 __device__ __forceinline__ void

@@ -57,11 +57,8 @@
 #endif
 #define HASHJOIN_NWAVES		(HASHJOIN_BLOCK / STROM_WAVE)
 #define HASHJOIN_TILE_ROWS	(HASHJOIN_BLOCK * 4 * HASHJOIN_QUADS)
-#define HASHJOIN_MAXRELS	8
 
-#define HASHJOIN_MODE_HASH		0
-#define HASHJOIN_MODE_DIRECT	1
-#define HASHJOIN_MODE_KEYED		2
+#include "strom_ctl.h"		/* the probe index, the join modes and the slot-record specs: the host fills them */
 
 /* KEYED slot: { x = offset of the key's first entry, y = tag (0 empty, 1 being
  * written by the index build, 2 ready), z|w = the key's canonical 64-bit image } */
@@ -69,36 +66,6 @@ typedef cl_uint hashjoin_keyed_slot __attribute__((ext_vector_type(4)));
 #define HASHJOIN_KEYED_EMPTY	0u
 #define HASHJOIN_KEYED_BUSY		1u
 #define HASHJOIN_KEYED_READY	2u
-
-/* probe index; gpuhashjoin.cpp mirrors these structs */
-struct hashjoin_index_rel {
-	cl_uint		mode;
-	cl_uint		nslots;			/* HASH / KEYED: power of two; DIRECT: key range */
-	cl_long		key_min;
-	cl_uint		unique;			/* no chain longer than one entry */
-	cl_uint		slots_off;		/* bytes from the index base to cl_uint slots[] */
-	cl_uint		nentries;
-	/*
-	 * DIRECT + unique keys: the same slots in THREE bytes each -- (entry offset >> 3; entries are
-	 * LONGALIGNed, KERN_HASHENTRY_SIZE_BY_TLEN) -- when the table is below 2^27 bytes; 0 = none.
-	 * A slot array is probed at random by every CU of an XCD: what counts is whether it fits that
-	 * XCD's 4 MB L2 next to the stream.  1.25e6 key values (BASELINE configs[2]) are 5.0 MB as
-	 * cl_uint -- one probe in three went to HBM for a 64-byte line -- and 3.75 MB like this.
-	 * Made by hashjoin_narrow_slots_kernel, read by gpuhashjoin_main_fast_narrow.
-	 */
-	cl_uint		slots3_off;
-};
-struct hashjoin_index {
-	cl_uint		nrels;
-	cl_uint		__pad[3];
-	hashjoin_index_rel rel[HASHJOIN_MAXRELS];
-};
-struct hashjoin_build_stats {
-	cl_long		key_min;
-	cl_long		key_max;
-	cl_uint		nentries;
-	cl_uint		intlike;
-};
 
 struct strom_kparams {
 #define X(idx,NAME)	pg_##NAME##_t KPARAM_##idx;
@@ -1529,16 +1496,6 @@ hashjoin_build_dimcol_kernel(const kern_multihash *kmhash, const hashjoin_index 
  * (gpupreagg_dense_lookup): with separate arrays every row costs one L2
  * request per array, and that kernel is bound by the L2 request rate.
  * ====================================================================== */
-struct hashjoin_dimrec_spec {
-	cl_uint		ncols;
-	cl_uint		reclen;
-	struct {
-		cl_int		col;			/* inner column, 0-based */
-		cl_int		attlen;
-		cl_uint		offset;			/* of the value inside the record */
-		cl_uint		__pad;
-	} c[16];
-};
 
 extern "C" __global__ void
 __launch_bounds__(256)
@@ -1607,19 +1564,6 @@ hashjoin_build_dimrec_kernel(const kern_multihash *kmhash, const hashjoin_index 
  * The presence / NULL bits sit where the standard record's flags word has
  * them, so a consumer tests them the same way.
  * ====================================================================== */
-struct hashjoin_dimrec_range {
-	cl_long		vmin[16];
-	cl_long		vmax[16];
-	cl_uint		nvalues[16];
-};
-
-struct hashjoin_dimrec_narrow_spec {
-	cl_uint		ncols;
-	cl_uint		reclen;				/* 2 or 4 */
-	cl_uint		shift[16];
-	cl_uint		mask[16];
-	cl_long		vmin[16];
-};
 
 STROM_DEVICE cl_long
 hashjoin_dimrec_value(const char *rec, cl_uint offset, cl_int attlen)
@@ -1640,10 +1584,10 @@ hashjoin_dimrec_minmax_kernel(const hashjoin_dimrec_spec *spec, const char *recs
 {
 	cl_uint		ncols = spec->ncols;
 	cl_uint		reclen = spec->reclen;
-	cl_long		my_min[16], my_max[16];
+	cl_long		my_min[HASHJOIN_DIMREC_MAXCOLS], my_max[HASHJOIN_DIMREC_MAXCOLS];
 	cl_uint		seen = 0;
 
-	for (int i = 0; i < 16; i++)
+	for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
 	{
 		my_min[i] = 0x7fffffffffffffffL;
 		my_max[i] = -0x7fffffffffffffffL - 1;
@@ -1655,7 +1599,7 @@ hashjoin_dimrec_minmax_kernel(const hashjoin_dimrec_spec *spec, const char *recs
 		if (!(flags & 1u))
 			continue;
 #pragma unroll
-		for (int i = 0; i < 16; i++)
+		for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
 		{
 			if (i < (int)ncols && !(flags & (2u << i)))
 			{
@@ -1670,7 +1614,7 @@ hashjoin_dimrec_minmax_kernel(const hashjoin_dimrec_spec *spec, const char *recs
 	{
 		seen |= (cl_uint)__shfl_xor((int)seen, off, STROM_WAVE);
 #pragma unroll
-		for (int i = 0; i < 16; i++)
+		for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
 		{
 			cl_long	omin = __shfl_xor(my_min[i], off, STROM_WAVE);
 			cl_long	omax = __shfl_xor(my_max[i], off, STROM_WAVE);
@@ -1681,7 +1625,7 @@ hashjoin_dimrec_minmax_kernel(const hashjoin_dimrec_spec *spec, const char *recs
 	if ((threadIdx.x & (STROM_WAVE - 1)) == 0)
 	{
 #pragma unroll
-		for (int i = 0; i < 16; i++)
+		for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
 		{
 			if (!(seen & (1u << i)))
 				continue;

@@ -32,18 +32,7 @@
 #ifndef STROM_MERGE_DEVICE_H
 #define STROM_MERGE_DEVICE_H
 
-#define PREAGG_MERGE_MAXAGGS	31
-
-typedef struct {
-	cl_uint		ngroups;
-	cl_uint		naggs;
-	cl_uint		op[PREAGG_MERGE_MAXAGGS];
-	cl_uint		__pad;
-	cl_ulong	vals_off[PREAGG_MERGE_MAXAGGS];		/* byte offset of section 1+a in the table */
-	cl_ulong	hi_off[PREAGG_MERGE_MAXAGGS];		/* op 1: byte offset of the sum's high-word section */
-	cl_uint		mid_idx[PREAGG_MERGE_MAXAGGS];		/* op 1: which ngroups-long lane of 'mid' takes bits 32..63 */
-	cl_uint		__pad2;
-} preagg_merge_spec;
+#include "strom_ctl.h"		/* preagg_merge_spec, preagg_export_spec: the host fills them */
 
 #define PREAGG_MERGE_SIGN	0x8000000000000000UL
 
@@ -176,23 +165,6 @@ preagg_merge_apply(void *dst, const void *src, cl_ulong count, cl_uint kind)
  * value of len bytes, 3 float8 sum (float4: narrowed), 4 float min / max (order-preserving key),
  * 5 integer sum {vals_off: low word, hi_off: high word}.
  */
-typedef struct {
-	cl_uint		ngroups;
-	cl_uint		ncols;
-	cl_uint		stride;
-	cl_uint		nkeys;
-	cl_long		key_min[8];
-	cl_uint		key_range[8];
-	cl_uint		key_stride[8];
-	struct {
-		cl_uint		kind;
-		cl_uint		len;			/* bytes of the datum */
-		cl_uint		which;			/* key number, or the aggregate's has-value bit (1 + a) */
-		cl_uint		float4;
-		cl_ulong	vals_off;
-		cl_ulong	hi_off;
-	} col[64];
-} preagg_export_spec;
 
 extern "C" __global__ void
 __launch_bounds__(256)

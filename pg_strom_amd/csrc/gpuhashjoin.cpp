@@ -17,32 +17,6 @@
 
 using namespace strom;
 
-namespace {
-
-/* mirror strom_hashjoin.h */
-struct index_rel {
-	cl_uint		mode;
-	cl_uint		nslots;
-	cl_long		key_min;
-	cl_uint		unique;
-	cl_uint		slots_off;
-	cl_uint		nentries;
-	cl_uint		slots3_off;		/* DIRECT + unique: the 3-byte slot array, 0 = none */
-};
-struct index_head {
-	cl_uint		nrels;
-	cl_uint		__pad[3];
-	index_rel	rel[8];
-};
-struct build_stats {
-	cl_long		key_min;
-	cl_long		key_max;
-	cl_uint		nentries;
-	cl_uint		intlike;
-};
-
-}	/* namespace */
-
 struct strom_hashjoin_table {
 	strom_devprog_key	key = 0;
 	Program			   *prog = nullptr;
@@ -51,9 +25,9 @@ struct strom_hashjoin_table {
 	size_t				kmhash_len = 0;
 	char			   *d_index = nullptr;
 	size_t				index_len = 0;
-	index_head			head;
+	hashjoin_index			head;
 	int					ntables = 0;
-	cl_uint				rel_ncols[8] = {};	/* columns of each inner relation (host-side request validation) */
+	cl_uint				rel_ncols[HASHJOIN_MAXRELS] = {};	/* columns of each inner relation (host-side request validation) */
 	std::atomic<int>	refcnt{1};
 	/* inner columns by slot for the COLUMN projection (DIRECT index, unique
 	 * keys): (0-based column, attlen) -> {values, isnull}, built on first use */
@@ -78,7 +52,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 	*p_errcode = 0;
 	Program *prog = lookup_program(key);
 	Device *dev = get_device(dindex);
-	if (!prog || !dev || !kmhash || kmhash->ntables < 1 || kmhash->ntables > 8 ||
+	if (!prog || !dev || !kmhash || kmhash->ntables < 1 || kmhash->ntables > HASHJOIN_MAXRELS ||
 		length < sizeof(kern_multihash))
 	{
 		*p_errcode = (!dev ? StromError_ServerNotReady : StromError_BadRequestMessage);
@@ -86,7 +60,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 	}
 	/* the image is about to be walked by kernels: every offset in it must
 	 * stay inside 'length' (a faulting kernel takes the host process down) */
-	cl_uint		rel_ncols[8] = {};
+	cl_uint		rel_ncols[HASHJOIN_MAXRELS] = {};
 	{
 		size_t	mh_head = offsetof(kern_multihash, htable_offset) + sizeof(cl_uint) * (size_t)kmhash->ntables;
 		bool	sane = (mh_head <= length);
@@ -152,11 +126,11 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 	if (hipMemcpyAsync(tbl->d_kmhash, kmhash, length, hipMemcpyHostToDevice, stream) != hipSuccess)
 		return fail(StromError_HipInternal);
 	/* step 1: per relation entry count and key range */
-	build_stats *d_stats = (build_stats *)dev->pool.alloc(sizeof(build_stats) * 8);
+	hashjoin_build_stats *d_stats = (hashjoin_build_stats *)dev->pool.alloc(sizeof(hashjoin_build_stats) * HASHJOIN_MAXRELS);
 	if (!d_stats)
 		return fail(StromError_OutOfMemory);
-	build_stats h_stats[8];
-	for (int t = 0; t < 8; t++)
+	hashjoin_build_stats h_stats[HASHJOIN_MAXRELS];
+	for (int t = 0; t < HASHJOIN_MAXRELS; t++)
 	{
 		h_stats[t].key_min = 0x7fffffffffffffffL;
 		h_stats[t].key_max = -0x7fffffffffffffffL - 1;
@@ -181,11 +155,11 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 	/* step 2: choose the index form per relation, lay the slots out */
 	memset(&tbl->head, 0, sizeof(tbl->head));
 	tbl->head.nrels = tbl->ntables;
-	size_t	off = STROM_TYPEALIGN(256, sizeof(index_head));
+	size_t	off = STROM_TYPEALIGN(256, sizeof(hashjoin_index));
 	bool	force_hash = (getenv("STROM_HASHJOIN_FORCE_HASH") != nullptr);
 	for (int t = 0; t < tbl->ntables; t++)
 	{
-		index_rel  &ir = tbl->head.rel[t];
+		hashjoin_index_rel  &ir = tbl->head.rel[t];
 		cl_ulong	n = h_stats[t].nentries;
 		bool		direct = false;
 		if (!force_hash && h_stats[t].intlike && n > 0 && h_stats[t].key_max >= h_stats[t].key_min)
@@ -196,7 +170,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 			if (range <= (1UL << 27) && range <= std::max<cl_ulong>(8 * n, 1UL << 16))
 			{
 				direct = true;
-				ir.mode = 1;
+				ir.mode = HASHJOIN_MODE_DIRECT;
 				ir.nslots = (cl_uint)range;
 				ir.key_min = h_stats[t].key_min;
 			}
@@ -214,7 +188,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 			char	def[48];
 			snprintf(def, sizeof(def), "#define HASHJOIN_KEYED_OK_%d 1\n", t + 1);
 			bool	keyed = (strstr(prog->source.c_str(), def) != nullptr && !getenv("STROM_HASHJOIN_NO_KEYED"));
-			ir.mode = (keyed ? 2 : 0);
+			ir.mode = (keyed ? HASHJOIN_MODE_KEYED : HASHJOIN_MODE_HASH);
 			ir.nslots = (cl_uint)slots;
 			ir.key_min = 0;
 			if (keyed)
@@ -240,7 +214,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 	if (!tbl->d_index)
 		return fail(StromError_OutOfMemory);
 	ok = (hipMemsetAsync(tbl->d_index, 0, off, stream) == hipSuccess &&
-		  hipMemcpyAsync(tbl->d_index, &tbl->head, sizeof(index_head), hipMemcpyHostToDevice, stream) == hipSuccess);
+		  hipMemcpyAsync(tbl->d_index, &tbl->head, sizeof(hashjoin_index), hipMemcpyHostToDevice, stream) == hipSuccess);
 	for (int t = 0; ok && t < tbl->ntables; t++)
 	{
 		void   *a_km = tbl->d_kmhash;
@@ -249,7 +223,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 		void   *args[] = { &a_km, &a_depth, &a_ix };
 		ok = (hipModuleLaunchKernel(fn_index, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess);
 	}
-	ok = ok && hipMemcpyAsync(&tbl->head, tbl->d_index, sizeof(index_head), hipMemcpyDeviceToHost, stream) == hipSuccess
+	ok = ok && hipMemcpyAsync(&tbl->head, tbl->d_index, sizeof(hashjoin_index), hipMemcpyDeviceToHost, stream) == hipSuccess
 		&& hipStreamSynchronize(stream) == hipSuccess;
 	if (!ok)
 		return fail(StromError_HipInternal);
@@ -259,7 +233,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 		hipFunction_t fn_narrow = nullptr;
 		for (int t = 0; ok && t < tbl->ntables; t++)
 		{
-			index_rel  &ir = tbl->head.rel[t];
+			hashjoin_index_rel  &ir = tbl->head.rel[t];
 			if (ir.slots3_off == 0)
 				continue;
 			if (!ir.unique || (!fn_narrow && !(fn_narrow = prog->get_function(dev, "hashjoin_narrow_slots_kernel", &errcode))))
@@ -274,7 +248,7 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 			ok = (hipModuleLaunchKernel(fn_narrow, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess);
 		}
 		if (ok && head_changed)
-			ok = (hipMemcpyAsync(tbl->d_index, &tbl->head, sizeof(index_head), hipMemcpyHostToDevice, stream) == hipSuccess);
+			ok = (hipMemcpyAsync(tbl->d_index, &tbl->head, sizeof(hashjoin_index), hipMemcpyHostToDevice, stream) == hipSuccess);
 		if (!ok || hipStreamSynchronize(stream) != hipSuccess)
 			return fail(StromError_HipInternal);
 	}
@@ -314,7 +288,7 @@ strom_hashjoin_table_info(strom_hashjoin_table *tbl, int depth,
 {
 	if (!tbl || depth < 1 || depth > tbl->ntables)
 		return StromError_BadRequestMessage;
-	const index_rel &ir = tbl->head.rel[depth - 1];
+	const hashjoin_index_rel &ir = tbl->head.rel[depth - 1];
 	if (p_mode) *p_mode = (int)ir.mode;
 	if (p_nslots) *p_nslots = ir.nslots;
 	if (p_unique) *p_unique = (int)ir.unique;
@@ -379,11 +353,11 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		task->stream = dev->streams[0];
 	else
 		task->stream = dev->streams[1 + dev->next_stream++ % (dev->streams.size() - 1)];
-	bool	fast = (tbl->ntables == 1 && (tbl->head.rel[0].mode == 1 || tbl->head.rel[0].mode == 2) &&
+	bool	fast = (tbl->ntables == 1 && (tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT || tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED) &&
 					tbl->head.rel[0].unique &&
 					req.format == KDS_FORMAT_COLUMN && req.krowmap == nullptr && req.rowmap_dev == nullptr &&
 					!getenv("STROM_HASHJOIN_NO_FAST"));
-	bool	fast_keyed = (fast && tbl->head.rel[0].mode == 2);	/* sparse integer keys: KEYED index */
+	bool	fast_keyed = (fast && tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED);	/* sparse integer keys: KEYED index */
 	hipFunction_t fn = nullptr;
 	if (fast)
 	{
@@ -839,7 +813,7 @@ int
 strom::hashjoin_table_dimcol(strom_hashjoin_table *tbl, int col, int attlen, void **p_values, void **p_isnull)
 {
 	Device *dev = tbl->dev;
-	if (tbl->ntables != 1 || tbl->head.rel[0].mode != 1 || !tbl->head.rel[0].unique ||
+	if (tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique ||
 		!(attlen == 1 || attlen == 2 || attlen == 4 || attlen == 8))
 		return StromError_BadRequestMessage;
 	std::lock_guard<std::mutex> g(tbl->dim_lock);
@@ -893,13 +867,10 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 							  unsigned *offsets, void **p_recs, unsigned *p_reclen,
 							  const int *narrowable, dimrec_narrow *narrow)
 {
-	struct spec_image {
-		cl_uint		ncols, reclen;
-		struct { cl_int col, attlen; cl_uint offset, pad; } c[16];
-	} spec;
+	hashjoin_dimrec_spec spec;
 	Device *dev = tbl->dev;
 
-	if (tbl->ntables != 1 || tbl->head.rel[0].mode != 1 || !tbl->head.rel[0].unique || n < 0 || n > 16)
+	if (tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique || n < 0 || n > HASHJOIN_DIMREC_MAXCOLS)
 		return StromError_BadRequestMessage;
 	memset(&spec, 0, sizeof(spec));
 	unsigned	off = 4;
@@ -958,7 +929,7 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 	*p_reclen = it->second.second;
 	if (narrow)
 	{
-		narrow->reclen = 0;
+		narrow->spec.reclen = 0;
 		bool	candidate = (narrowable != nullptr && n >= 1 && !getenv("STROM_HASHJOIN_NO_NARROW_RECS"));
 		for (int i = 0; candidate && i < n; i++)
 			candidate = (narrowable[i] != 0);
@@ -969,9 +940,9 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 			 * ranges of the wanted columns over the present, non-NULL values -> field widths;
 			 * 1 + n flag bits + the fields must fit 16 or 32 bits
 			 */
-			struct range_image { cl_long vmin[16]; cl_long vmax[16]; cl_uint nvalues[16]; } rg;
-			struct nspec_image { cl_uint ncols, reclen; cl_uint shift[16]; cl_uint mask[16]; cl_long vmin[16]; } ns;
+			hashjoin_dimrec_range rg;
 			dimrec_narrow	nw;
+			hashjoin_dimrec_narrow_spec &ns = nw.spec;
 			int			errcode = 0;
 			cl_uint		nslots = tbl->head.rel[0].nslots;
 			hipStream_t	stream = dev->streams[0];
@@ -984,7 +955,7 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 			unsigned	grid = std::max(1u, std::min<unsigned>((nslots + 255) / 256,
 														   (unsigned)dev->prop.multiProcessorCount * 8));
 			memset(&rg, 0, sizeof(rg));
-			for (int i = 0; i < 16; i++)
+			for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
 			{
 				rg.vmin[i] = INT64_MAX;
 				rg.vmax[i] = INT64_MIN;
@@ -1015,16 +986,16 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 					ok = false;
 					break;
 				}
-				ns.shift[i] = nw.shift[i] = bits;
-				ns.mask[i] = nw.mask[i] = (w == 0 ? 0u : (cl_uint)((1UL << w) - 1));
-				ns.vmin[i] = nw.vmin[i] = (rg.nvalues[i] ? rg.vmin[i] : 0);
+				ns.shift[i] = bits;
+				ns.mask[i] = (w == 0 ? 0u : (cl_uint)((1UL << w) - 1));
+				ns.vmin[i] = (rg.nvalues[i] ? rg.vmin[i] : 0);
 				bits += w;
 			}
 			if (ok)
 			{
 				ns.ncols = (cl_uint)n;
-				ns.reclen = nw.reclen = (bits <= 16 ? 2 : 4);
-				char   *d_out = (char *)dev->pool.alloc((size_t)nw.reclen * nslots + 64);
+				ns.reclen = (bits <= 16 ? 2 : 4);
+				char   *d_out = (char *)dev->pool.alloc((size_t)ns.reclen * nslots + 64);
 				const void *a_spec = d_spec;
 				const void *a_recs = it->second.first;
 				const void *a_ns = d_ns;
@@ -1040,7 +1011,7 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 					dev->pool.release(d_out);
 			}
 			if (!ok)
-				nw.reclen = 0;
+				ns.reclen = 0;
 			if (d_spec) dev->pool.release(d_spec);
 			if (d_rg) dev->pool.release(d_rg);
 			if (d_ns) dev->pool.release(d_ns);
@@ -1058,7 +1029,7 @@ int
 strom::hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 								  int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual)
 {
-	if (!tbl || tbl->ntables != 1 || tbl->head.rel[0].mode != 1 || !tbl->head.rel[0].unique ||
+	if (!tbl || tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique ||
 		!strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_ELIGIBLE 1"))
 		return StromError_BadRequestMessage;
 	const char *p = strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_OUTER_KEY_ATTNO ");
@@ -1207,7 +1178,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	 * slot-indexed arrays (hashjoin_build_dimcol_kernel) instead of the entries
 	 */
 	std::vector<cl_ulong> dimptr(2 * (size_t)ncols, 0);
-	bool	use_dim = (tbl->ntables == 1 && tbl->head.rel[0].mode == 1 && tbl->head.rel[0].unique &&
+	bool	use_dim = (tbl->ntables == 1 && tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT && tbl->head.rel[0].unique &&
 					   outer->head.format == KDS_FORMAT_COLUMN &&
 					   strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_ELIGIBLE 1") != nullptr &&
 					   !getenv("STROM_HASHJOIN_NO_DIMCOLS"));

@@ -28,23 +28,6 @@ static strom_gpupreagg *gpupreagg_exact_child(strom_gpupreagg *sess, int *p_errc
 
 namespace {
 
-/* mirrors struct gpupreagg_dense_ctl of strom_gpupreagg.h */
-struct dense_ctl {
-	cl_uint		ngroups;
-	cl_uint		nsplits;
-	cl_uint		groups_per_split;
-	cl_uint		nrep;
-	cl_uint		nslabs;
-	cl_uint		nkeys;
-	cl_ulong	slab_bytes;
-	cl_long		key_min[STROM_PREAGG_MAXKEYS];
-	cl_uint		key_range[STROM_PREAGG_MAXKEYS];
-	cl_uint		key_stride[STROM_PREAGG_MAXKEYS];
-	cl_ulong	remap;				/* device cl_uint[dense_ngroups], 0 = none */
-	cl_uint		dense_ngroups;
-	cl_uint		merge_ws;
-};
-
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }	/* namespace */
@@ -57,7 +40,7 @@ struct strom_gpupreagg {
 	std::vector<int>	agg_resno, key_resno;
 	std::vector<char>	kparams;			/* kern_parambuf image */
 	bool				has_domain = false;
-	dense_ctl			ctl;
+	gpupreagg_dense_ctl			ctl;
 	size_t				lds_bytes = 0;
 	size_t				table_bytes = 0;
 	char			   *table = nullptr;	/* resident table (device) */
@@ -86,7 +69,7 @@ struct strom_gpupreagg {
 	bool				packable = false;
 	std::vector<int>	pack_kind, pack_attno;
 	struct packed_geom {
-		dense_ctl	ctl;
+		gpupreagg_dense_ctl	ctl;
 		char	   *d_ctl = nullptr;
 		char	   *d_slabs = nullptr;		/* two buffers of nslabs * slab_bytes (see slab_turn) */
 		size_t		lds_bytes = 0;
@@ -126,40 +109,20 @@ struct strom_gpupreagg {
 	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (lookup_mapping_program) */
 	char			   *d_export_spec = nullptr;	/* preagg_export_spec of this table (fetch on the device) */
 
-	/* mirrors gpupreagg_image_offset / gpupreagg_table_offset of
-	 * strom_gpupreagg.h: section 0 = flags, 1+a = values of aggregate a,
-	 * 1+naggs = total */
-	size_t flag_width() const
-	{
-		size_t n = agg_resno.size();
-		return n <= 7 ? 1 : (n <= 15 ? 2 : 4);
-	}
+	/* the LDS / slab image of this session's aggregates (strom_ctl.h): section 0 = flags,
+	 * 1+a = values of aggregate a, 1+naggs = total */
 	size_t image_offset(int sec, cl_uint G, cl_uint REP) const
 	{
-		size_t	off = 0;
-		int		cur = 0;
-		if (sec == cur) return off;
-		off += align16(flag_width() * (size_t)G * REP); cur++;
-		for (int resno : agg_resno)
-		{
-			bool nrows = (targets[resno].kind == STROM_PREAGG_NROWS);
-			if (sec == cur) return off;
-			off += align16((nrows ? 4 : 8) * (size_t)G * REP);
-			cur++;
-		}
-		return off;
-	}
-	size_t table_offset(int sec, cl_uint N) const
-	{
-		size_t	flags = STROM_TYPEALIGN(256, sizeof(cl_uint) * (size_t)N);
-		size_t	vals = STROM_TYPEALIGN(256, 8 * (size_t)N);
-		if (sec == 0) return 0;
-		return flags + vals * (size_t)(sec - 1);
+		cl_uint	nrows_mask = 0;
+		for (size_t a = 0; a < agg_resno.size() && a < 32; a++)		/* (a flags word has a bit for 31) */
+			if (targets[agg_resno[a]].kind == STROM_PREAGG_NROWS)
+				nrows_mask |= 1u << a;
+		return gpupreagg_image_offset_of<size_t>(sec, G, REP, (int)agg_resno.size(), nrows_mask);
 	}
 	int nsections() const { return 1 + (int)agg_resno.size(); }
 	/* the table has one more section per integer sum: its high word (section 1 + naggs + j) */
 	int table_sections() const { return nsections() + nintsums; }
-	size_t table_hi_offset(int a, cl_uint N) const { return table_offset(nsections() + intsum_of[a], N); }
+	size_t table_hi_offset(int a, cl_uint N) const { return gpupreagg_table_offset(nsections() + intsum_of[a], N); }
 	bool is_intsum(int a) const { return intsum_of[a] >= 0; }
 };
 
@@ -202,7 +165,7 @@ int	setup_layout(strom_gpupreagg *sess);
 int
 setup_geometry(strom_gpupreagg *sess, const strom_preagg_domain *dom)
 {
-	dense_ctl  &ctl = sess->ctl;
+	gpupreagg_dense_ctl  &ctl = sess->ctl;
 
 	if (dom->nkeys != (int)sess->key_resno.size() || dom->nkeys > STROM_PREAGG_MAXKEYS)
 		return StromError_BadRequestMessage;
@@ -232,7 +195,7 @@ int
 setup_layout(strom_gpupreagg *sess)
 {
 	Device	   *dev = sess->dev;
-	dense_ctl  &ctl = sess->ctl;
+	gpupreagg_dense_ctl  &ctl = sess->ctl;
 	size_t		lds_budget = std::min<size_t>(dev->prop.sharedMemPerBlock, 160 * 1024) - 8192;	/* static LDS: remap stage, scan scratch */
 
 	if (const char *v = getenv("STROM_GPUPREAGG_LDS_BUDGET"))
@@ -308,7 +271,7 @@ setup_layout(strom_gpupreagg *sess)
 	if (sess->reg_groups == 2)
 		sess->lds_bytes = priv_bytes;
 	ctl.slab_bytes = STROM_TYPEALIGN(256, sess->image_offset(sess->nsections(), ctl.groups_per_split, 1));
-	sess->table_bytes = sess->table_offset(sess->table_sections(), ctl.ngroups);
+	sess->table_bytes = gpupreagg_table_offset(sess->table_sections(), ctl.ngroups);
 	/* work-groups: fill the CUs at the occupancy LDS allows */
 	size_t	per_cu = std::max<size_t>(1, std::min<size_t>((size_t)dev->prop.sharedMemPerBlock / (sess->lds_bytes + 4608),	/* + static LDS */
 														  2048 / sess->block));
@@ -354,48 +317,14 @@ alloc_session_buffers(strom_gpupreagg *sess)
 		if (hipMemset(sess->table, 0, sess->table_bytes) != hipSuccess)
 			return StromError_HipInternal;
 	}
-	sess->d_ctl = (char *)dev->pool.alloc(sizeof(dense_ctl));
+	sess->d_ctl = (char *)dev->pool.alloc(sizeof(gpupreagg_dense_ctl));
 	sess->d_slabs = (char *)dev->pool.alloc(2 * (size_t)sess->ctl.nslabs * sess->ctl.slab_bytes);
 	if (!sess->d_ctl || !sess->d_slabs)
 		return StromError_OutOfMemory;
-	if (hipMemcpy(sess->d_ctl, &sess->ctl, sizeof(dense_ctl), hipMemcpyHostToDevice) != hipSuccess)
+	if (hipMemcpy(sess->d_ctl, &sess->ctl, sizeof(gpupreagg_dense_ctl), hipMemcpyHostToDevice) != hipSuccess)
 		return StromError_HipInternal;
 	return 0;
 }
-
-/* host image of struct gpupreagg_joined_map (strom_gpupreagg.h) */
-struct joined_map_image {
-	cl_uint		ncols;
-	cl_int		key_col;
-	cl_int		key_attlen;
-	cl_uint		nslots;
-	cl_long		key_min;
-	struct {
-		cl_int		depth;
-		cl_int		col;
-		cl_ulong	dimvalues;
-		cl_ulong	dimisnull;
-	} c[64];
-	cl_ulong	recs;
-	cl_uint		reclen;
-	cl_uint		narrow;
-	cl_uint		nshift[64];
-	cl_uint		nmask[64];
-	cl_long		nmin[64];
-};
-
-/* mirrors struct gpupreagg_pack_ctl of strom_gpupreagg.h */
-struct pack_ctl {
-	cl_uint		count_shift;
-	cl_uint		nwords;
-	cl_uint		spill_at;
-	cl_uint		count_limit;
-	cl_uint		shift[32];
-	cl_uint		word[32];
-	cl_ulong	mask[32];
-	cl_ulong	vmax[32];
-	cl_long		bias[32];
-};
 
 int
 bits_for(cl_ulong v)			/* bits needed to hold values 0..v */
@@ -416,10 +345,10 @@ bits_for(cl_ulong v)			/* bits needed to hold values 0..v */
  */
 strom_gpupreagg::packed_geom *
 packed_plan(strom_gpupreagg *sess, hipFunction_t fn_packed, const kern_coldir *coldir, cl_uint ncols,
-			cl_uint nitems, pack_ctl *pk)
+			cl_uint nitems, gpupreagg_pack_ctl *pk)
 {
 	Device	   *dev = sess->dev;
-	dense_ctl  &std_ctl = sess->ctl;
+	gpupreagg_dense_ctl  &std_ctl = sess->ctl;
 
 	if (!sess->packable || !fn_packed || !coldir || std_ctl.remap != 0 || std_ctl.nsplits < 2 ||
 		getenv("STROM_GPUPREAGG_NO_PACKED"))
@@ -545,10 +474,10 @@ packed_plan(strom_gpupreagg *sess, hipFunction_t fn_packed, const kern_coldir *c
 		geom.ctl.slab_bytes = STROM_TYPEALIGN(256, sess->image_offset(sess->nsections(), G, 1));
 		geom.lds_bytes = (size_t)nwords * align16(8 * (size_t)G);
 		(void)hipSetDevice(dev->hip_id);
-		geom.d_ctl = (char *)dev->pool.alloc(sizeof(dense_ctl));
+		geom.d_ctl = (char *)dev->pool.alloc(sizeof(gpupreagg_dense_ctl));
 		geom.d_slabs = (char *)dev->pool.alloc(2 * (size_t)geom.ctl.nslabs * geom.ctl.slab_bytes);
 		if (!geom.d_ctl || !geom.d_slabs ||
-			hipMemcpy(geom.d_ctl, &geom.ctl, sizeof(dense_ctl), hipMemcpyHostToDevice) != hipSuccess)
+			hipMemcpy(geom.d_ctl, &geom.ctl, sizeof(gpupreagg_dense_ctl), hipMemcpyHostToDevice) != hipSuccess)
 		{
 			if (geom.d_ctl) dev->pool.release(geom.d_ctl);
 			if (geom.d_slabs) dev->pool.release(geom.d_slabs);
@@ -582,7 +511,7 @@ struct preagg_request {
 	void			   *joined_buffer = nullptr;	/* the join's device image, owned by this request now */
 	bool				lookup = false;				/* no result pairs: the join is a lookup in the aggregate's pass */
 	Program			   *prog = nullptr;				/* lookup: the session's program built for this column mapping */
-	std::shared_ptr<std::vector<char>> joined_map;	/* host image of gpupreagg_joined_map */
+	std::shared_ptr<std::vector<char>> joined_map;	/* a gpupreagg_joined_map */
 	/* hashed, exact fold (gpupreagg_hashed_exact): 'sess' is a scratch session of this one */
 	strom_gpupreagg	   *exact_parent = nullptr;
 };
@@ -681,12 +610,12 @@ eval_sum_bound(const std::string &formula, const kern_coldir *cd, cl_uint ncd)
  * request of a mapping parks behind its build like any request behind a cold program.
  */
 Program *
-lookup_mapping_program(strom_gpupreagg *sess, const joined_map_image *jm)
+lookup_mapping_program(strom_gpupreagg *sess, const gpupreagg_joined_map *jm)
 {
 	if (getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
 		return nullptr;						/* the run-time form: any mapping, no build */
 	cl_ulong	inner_mask = 0;
-	for (cl_uint i = 0; i < jm->ncols && i < 64; i++)
+	for (cl_uint i = 0; i < jm->ncols && i < GPUPREAGG_JOINED_MAXCOLS; i++)
 		if (jm->c[i].depth != 0)
 			inner_mask |= (1UL << i);
 	char		defs[512];
@@ -783,7 +712,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 	/* what is known about the integer sums' inputs before the fold measures the rest */
 	cl_uint		magbits = sess->static_magbits;
 	/* packed accumulators for this chunk?  (fewer id-range roles: see packed_plan) */
-	pack_ctl	pk;
+	gpupreagg_pack_ctl	pk;
 	strom_gpupreagg::packed_geom *packed = nullptr;
 	if ((use_lookup || (use_column && !use_reg)) && sess->packable && sess->ctl.nsplits > 1 && !checked)
 	{
@@ -808,7 +737,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 		{
 			/* the program's columns are virtual: an outer column brings its own
 			 * directory entry, an inner column counts as "may be NULL, no zone map" */
-			const joined_map_image *jm = (const joined_map_image *)req.joined_map->data();
+			const gpupreagg_joined_map *jm = (const gpupreagg_joined_map *)req.joined_map->data();
 			virt.resize(jm->ncols);
 			for (cl_uint i = 0; i < jm->ncols; i++)
 			{
@@ -834,7 +763,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 	}
 	/* kern_gpupreagg image: {status, sortbuf_len, pad, kern_parambuf} [+ the pack control block] */
 	size_t	kg_len = STROMALIGN(offsetof(kern_gpupreagg, kparams) + sess->kparams.size());
-	size_t	send_len = kg_len + (packed ? STROMALIGN(sizeof(pack_ctl)) : 0);
+	size_t	send_len = kg_len + (packed ? STROMALIGN(sizeof(gpupreagg_pack_ctl)) : 0);
 	char   *stage = dev->pinned.alloc();
 	char   *d_kg = (char *)dev->pool.alloc(send_len);
 	if (!stage || !d_kg || send_len + 64 > PinnedPool::BLOCK)
@@ -855,7 +784,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 		 * folds at most -- tiles (or, row by row, blocks) are dealt round-robin to the work-groups
 		 * of a role; one unit of slack
 		 */
-		const dense_ctl &g = (packed ? packed->ctl : sess->ctl);
+		const gpupreagg_dense_ctl &g = (packed ? packed->ctl : sess->ctl);
 		size_t		unit = (use_reg ? (size_t)256 * 4 * sess->quads
 							: (use_column || use_lookup) ? (size_t)sess->block * 4 * sess->quads
 							: (size_t)sess->block);
@@ -867,7 +796,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 		 * here, the fold does not measure them (top bit of the second word; the streaming kernels
 		 * read it, the row-at-a-time ones measure as always)
 		 */
-		cl_uint		zone_bounded = 0;
+		bool		zone_bounded = false;
 		if (!packed && !checked && (use_column || use_reg))
 		{
 			std::shared_ptr<std::vector<kern_coldir>> snap;
@@ -914,13 +843,11 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 			}
 			if (all && any)
 			{
-				zone_bounded = 0x80000000u;
+				zone_bounded = true;
 				magbits = std::max(magbits, zbits);
 			}
 		}
-		cl_uint		words[2] = { magbits, (cl_uint)std::min<size_t>(wg_rows, 0x7fffffffUL) | zone_bounded };
-		((kern_gpupreagg *)stage)->sortbuf_len = (cl_int)req.nrows;
-		memcpy(((kern_gpupreagg *)stage)->__padding, words, sizeof(words));
+		kern_gpupreagg_set_chunk_words((kern_gpupreagg *)stage, req.nrows, magbits, wg_rows, zone_bounded);
 	}
 	if (packed)
 		memcpy(stage + kg_len, &pk, sizeof(pk));
@@ -1017,7 +944,7 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 		const void *a_kds = d_kds;
 		const void *a_toast = nullptr;
 		const void *a_map = d_rowmap;
-		const dense_ctl &lctl = (packed ? packed->ctl : sess->ctl);		/* this launch's geometry */
+		const gpupreagg_dense_ctl &lctl = (packed ? packed->ctl : sess->ctl);		/* this launch's geometry */
 		void	   *a_ctl = (packed ? packed->d_ctl : sess->d_ctl);
 		void	   *a_slabs = (packed ? packed->d_slabs : sess->d_slabs) +
 			(size_t)turn * lctl.nslabs * lctl.slab_bytes;
@@ -1148,29 +1075,22 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
  * hashed GROUP BY (gpupreagg_hash_* of strom_gpupreagg.h)
  * ------------------------------------------------------------------ */
 
-/* host image of the table: head (GPUPREAGG_HASH_HEAD bytes), then one record
- * per slot { state, knull, flags, pad, keys[nkeys], vals[naggs] } */
-struct hash_layout {
-	std::vector<char> head;
-	size_t		stride;
-	size_t		total;
-};
+/* what a fold reads back of the head: capacity, nkeys and the two counters the kernels raise */
+const size_t HASH_HEAD_COUNTERS = offsetof(gpupreagg_hash_head, stride);
 
-const size_t HASH_HEAD_LEN = 256;
-
-hash_layout
-hash_table_layout(const strom_gpupreagg *sess, cl_uint capacity)
+/* the head of a table of 'capacity' slots as the host writes it (strom_ctl.h), and the table's bytes */
+gpupreagg_hash_head
+hash_table_head(const strom_gpupreagg *sess, cl_uint capacity, size_t *p_total)
 {
-	hash_layout	L;
+	gpupreagg_hash_head head = {};
 	size_t		nkeys = sess->key_resno.size(), naggs = sess->agg_resno.size();
-	size_t		reclen = 16 + 8 * (nkeys + naggs);
 
-	L.stride = (reclen <= 32 ? 32 : reclen <= 64 ? 64 : (reclen + 127) / 128 * 128);
-	L.total = HASH_HEAD_LEN + L.stride * (size_t)capacity;
-	L.head.assign(HASH_HEAD_LEN, 0);
-	cl_uint	words[6] = { capacity, (cl_uint)nkeys, 0, 0, (cl_uint)L.stride, (cl_uint)naggs };
-	memcpy(L.head.data(), words, sizeof(words));
-	return L;
+	head.capacity = capacity;
+	head.nkeys = (cl_uint)nkeys;
+	head.stride = (cl_uint)GPUPREAGG_HASH_STRIDE_OF(nkeys, naggs);
+	head.naggs = (cl_uint)naggs;
+	*p_total = GPUPREAGG_HASH_HEAD + (size_t)head.stride * capacity;
+	return head;
 }
 
 /* slots of the work-group's LDS table in front of the global one, and its bytes */
@@ -1178,13 +1098,13 @@ cl_uint
 hash_lds_slots(const strom_gpupreagg *sess, size_t *p_bytes, bool for_units = false)
 {
 	size_t		nkeys = sess->key_resno.size();
-	/* after the table: 256 queued row numbers per wave (GPUPREAGG_HASH_QUEUE, used with roles) */
-	size_t		queue = (for_units ? 16 /* the unit's flags */ : ((size_t)sess->block / 64) * 256 * sizeof(cl_uint));
+	/* after the table: GPUPREAGG_HASH_QUEUE queued row numbers per wave (used with roles) */
+	size_t		queue = (for_units ? 16 /* the unit's flags */ : ((size_t)sess->block / 64) * GPUPREAGG_HASH_QUEUE * sizeof(cl_uint));
 	auto fit = [&](size_t budget, size_t *p_b) -> cl_uint {
 		cl_uint	slots = 16384;
 		for (;;)
 		{
-			*p_b = sess->image_offset(sess->nsections(), slots, 1) + (size_t)slots * (8 + 8 * nkeys) + queue;
+			*p_b = sess->image_offset(sess->nsections(), slots, 1) + (size_t)slots * GPUPREAGG_HASH_LDS_ENTRY(nkeys) + queue;
 			if (*p_b <= budget || slots == 64)
 				return slots;
 			slots >>= 1;
@@ -1214,7 +1134,7 @@ hash_lds_slots(const strom_gpupreagg *sess, size_t *p_bytes, bool for_units = fa
 		cl_uint		want = (cl_uint)atoi(v);
 		if (want >= 64 && want <= 16384 && (want & (want - 1)) == 0)
 		{
-			*p_bytes = sess->image_offset(sess->nsections(), want, 1) + (size_t)want * (8 + 8 * nkeys) + queue;
+			*p_bytes = sess->image_offset(sess->nsections(), want, 1) + (size_t)want * GPUPREAGG_HASH_LDS_ENTRY(nkeys) + queue;
 			return want;
 		}
 	}
@@ -1234,19 +1154,20 @@ hash_table_new(strom_gpupreagg *sess, cl_uint capacity, char **p_tab, size_t *p_
 {
 	Device	   *dev = sess->dev;
 	hipStream_t	stream = dev->streams[0];
-	hash_layout	L = hash_table_layout(sess, capacity);
+	size_t		total = 0;
+	gpupreagg_hash_head head = hash_table_head(sess, capacity, &total);
 	int			errcode = 0;
 	hipFunction_t fn_init = sess->prog->get_function(dev, "gpupreagg_hash_init", &errcode);
 	if (!fn_init)
 		return errcode;
-	char   *tab = (reuse ? reuse : (char *)dev->pool.alloc(L.total));
+	char   *tab = (reuse ? reuse : (char *)dev->pool.alloc(total));
 	if (!tab)
 		return StromError_OutOfMemory;
 	/* the head is tiny: a synchronous copy from pageable memory is fine and keeps
 	 * the source alive */
-	if (hipMemsetAsync(tab, 0, L.total, stream) != hipSuccess ||
+	if (hipMemsetAsync(tab, 0, total, stream) != hipSuccess ||
 		hipStreamSynchronize(stream) != hipSuccess ||
-		hipMemcpy(tab, L.head.data(), L.head.size(), hipMemcpyHostToDevice) != hipSuccess)
+		hipMemcpy(tab, &head, sizeof(head), hipMemcpyHostToDevice) != hipSuccess)
 	{
 		if (!reuse) dev->pool.release(tab);
 		return StromError_HipInternal;
@@ -1261,7 +1182,7 @@ hash_table_new(strom_gpupreagg *sess, cl_uint capacity, char **p_tab, size_t *p_
 		return StromError_HipInternal;
 	}
 	*p_tab = tab;
-	*p_bytes = L.total;
+	*p_bytes = total;
 	return 0;
 }
 
@@ -1279,14 +1200,14 @@ hash_fill_limit(const strom_gpupreagg *sess, cl_ulong headroom)
 int
 hash_table_ngroups(strom_gpupreagg *sess, cl_uint *p_ngroups, cl_uint *p_overflow)
 {
-	cl_uint	words[4];
+	gpupreagg_hash_head head;
 	if (hipStreamSynchronize(sess->dev->streams[0]) != hipSuccess ||
-		hipMemcpy(words, sess->htab, sizeof(words), hipMemcpyDeviceToHost) != hipSuccess)
+		hipMemcpy(&head, sess->htab, HASH_HEAD_COUNTERS, hipMemcpyDeviceToHost) != hipSuccess)
 		return StromError_HipInternal;
-	*p_ngroups = words[2];
-	sess->groups_known = std::max<cl_uint>(sess->groups_known, words[2]);
+	*p_ngroups = head.ngroups;
+	sess->groups_known = std::max<cl_uint>(sess->groups_known, head.ngroups);
 	if (p_overflow)
-		*p_overflow = words[3];
+		*p_overflow = head.overflow;
 	return 0;
 }
 
@@ -1358,8 +1279,8 @@ hash_sum_refresh(strom_gpupreagg *sess)
 	void	   *args[] = { &a_tab };
 	unsigned	grid = std::max(1u, std::min<unsigned>((sess->hash_capacity + 255) / 256,
 													(unsigned)dev->prop.multiProcessorCount * 8));
-	/* sum_bound[2] sits 32 bytes into the head (struct gpupreagg_hash_head) */
-	if (hipMemsetAsync(sess->htab + 32, 0, 16, dev->streams[0]) != hipSuccess ||
+	if (hipMemsetAsync(sess->htab + offsetof(gpupreagg_hash_head, sum_bound), 0, sizeof(gpupreagg_hash_head::sum_bound),
+					   dev->streams[0]) != hipSuccess ||
 		hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, dev->streams[0], args, nullptr) != hipSuccess)
 		return StromError_HipInternal;
 	return 0;
@@ -1379,7 +1300,7 @@ hash_sum_measured_bound(strom_gpupreagg *sess, cl_ulong *p_bound)
 	if (rc)
 		return rc;
 	if (hipStreamSynchronize(sess->dev->streams[0]) != hipSuccess ||
-		hipMemcpy(p_bound, sess->htab + 32, sizeof(cl_ulong), hipMemcpyDeviceToHost) != hipSuccess)
+		hipMemcpy(p_bound, sess->htab + offsetof(gpupreagg_hash_head, sum_bound), sizeof(cl_ulong), hipMemcpyDeviceToHost) != hipSuccess)
 		return StromError_HipInternal;
 	return 0;
 }
@@ -1515,8 +1436,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 	memcpy(stage + offsetof(kern_gpupreagg, kparams), sess->kparams.data(), sess->kparams.size());
 	/* integer sums never wrap (strom_gpupreagg.h): rows of the request, what is known about
 	 * the inputs before the check pass measures the rest */
-	((kern_gpupreagg *)stage)->sortbuf_len = (cl_int)req.nrows;
-	memcpy(((kern_gpupreagg *)stage)->__padding, &sess->static_magbits, sizeof(cl_uint));
+	kern_gpupreagg_set_chunk_words((kern_gpupreagg *)stage, req.nrows, sess->static_magbits, 0, false);
 	/* the fold's turn (gpupreagg_hash_sum_account): parity; 4 = second attempt, after the
 	 * bound was measured; relaunches for deferred rows add 2 */
 	/* (bit 2 -- "a failed proof is final: CpuReCheck" -- is no longer asked for: the host sends an
@@ -1640,35 +1560,34 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			nvals += (sess->targets[resno].kind != STROM_PREAGG_NROWS ? 1 : 0);
 		size_t		reclen = 8 * (1 + sess->key_resno.size() + nvals);
 		cl_uint		max_units = nparts + nrows / unit_rows + 1;
-		struct part_ctl { cl_uint nparts, pshift, unit_rows, nunits, nrecords, deferred, max_units, reclen; } ctl_img;
-		ctl_img = part_ctl{ nparts, (log2cap > log2parts ? log2cap - log2parts : 0), unit_rows, 0, 0, 0, max_units, (cl_uint)reclen };
+		gpupreagg_part_ctl ctl_img = { nparts, (log2cap > log2parts ? log2cap - log2parts : 0), unit_rows, 0, 0, 0, max_units, (cl_uint)reclen };
 		/* ctl | hist[P] | cursor[P] | units[2 * max_units] | two redo lists of max_units */
-		size_t		ctl_len = sizeof(part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)4 * max_units);
+		size_t		ctl_len = sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)4 * max_units);
 		char	   *d_ctl = (char *)dev->pool.alloc(ctl_len);
 		char	   *d_partmap = (char *)dev->pool.alloc(STROMALIGN((size_t)nrows * sizeof(cl_ushort)));
 		char	   *d_records = (char *)dev->pool.alloc((size_t)nrows * reclen);
 		if (d_ctl) task->devbufs.push_back(d_ctl);
 		if (d_partmap) task->devbufs.push_back(d_partmap);
 		if (d_records) task->devbufs.push_back(d_records);
-		if (!d_ctl || !d_partmap || !d_records || kg_len + 128 + sizeof(part_ctl) > PinnedPool::BLOCK)
+		if (!d_ctl || !d_partmap || !d_records || kg_len + 128 + sizeof(gpupreagg_part_ctl) > PinnedPool::BLOCK)
 		{
 			task_fail(task, StromError_OutOfMemory);
 			return;
 		}
 		char	   *stage_ctl = stage + kg_len + 64;
 		memcpy(stage_ctl, &ctl_img, sizeof(ctl_img));
-		REQ_CHECK(hipMemsetAsync(d_ctl, 0, sizeof(part_ctl) + sizeof(cl_uint) * nparts, task->stream),
+		REQ_CHECK(hipMemsetAsync(d_ctl, 0, sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * nparts, task->stream),
 				  "reset partition counts");
-		REQ_CHECK(hipMemcpyAsync(d_ctl, stage_ctl, sizeof(part_ctl), hipMemcpyHostToDevice, task->stream),
+		REQ_CHECK(hipMemcpyAsync(d_ctl, stage_ctl, sizeof(gpupreagg_part_ctl), hipMemcpyHostToDevice, task->stream),
 				  "send partition plan");
 		void	   *a_kg = d_kg;
 		const void *a_kds = d_kds;
 		const void *a_toast = nullptr;
 		const void *a_map = d_rowmap;
 		void	   *a_ctl = d_ctl;
-		void	   *a_hist = d_ctl + sizeof(part_ctl);
-		void	   *a_cursor = d_ctl + sizeof(part_ctl) + sizeof(cl_uint) * nparts;
-		void	   *a_units = d_ctl + sizeof(part_ctl) + sizeof(cl_uint) * 2 * nparts;
+		void	   *a_hist = d_ctl + sizeof(gpupreagg_part_ctl);
+		void	   *a_cursor = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * nparts;
+		void	   *a_units = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * 2 * nparts;
 		void	   *a_partmap = d_partmap;
 		void	   *a_records = d_records;
 		unsigned	ncus = (unsigned)dev->prop.multiProcessorCount;
@@ -1752,7 +1671,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			if ((want == 256 || want == 512 || want == 1024) && (unsigned)want <= block)
 				fold_block = (unsigned)want;
 		}
-		char	   *d_lists = d_ctl + sizeof(part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)2 * max_units);
+		char	   *d_lists = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)2 * max_units);
 		void	   *a_todo = nullptr;
 		cl_uint		ntodo = 0;
 		for (int turn = 0;; turn++)
@@ -1780,7 +1699,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			void	   *a_tab = sess->htab;
 			void	   *a_redo = d_lists + sizeof(cl_uint) * (size_t)max_units * (turn & 1);
 			if (may_defer)
-				REQ_CHECK(hipMemsetAsync(d_ctl + offsetof(part_ctl, deferred), 0, sizeof(cl_uint), task->stream),
+				REQ_CHECK(hipMemsetAsync(d_ctl + offsetof(gpupreagg_part_ctl, deferred), 0, sizeof(cl_uint), task->stream),
 						  "reset the redo list");
 			cl_uint		a_turn = sum_turn | (turn > 0 ? 2u : 0u);
 			void	   *args[] = { &a_kg, &a_tab, &claim_limit, &a_ctl, &a_units, &a_records, &lds_slots,
@@ -1797,7 +1716,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 				break;
 			}
 			cl_uint		nredo = 0;
-			REQ_CHECK(hipMemcpyAsync(&nredo, d_ctl + offsetof(part_ctl, deferred), sizeof(cl_uint),
+			REQ_CHECK(hipMemcpyAsync(&nredo, d_ctl + offsetof(gpupreagg_part_ctl, deferred), sizeof(cl_uint),
 									 hipMemcpyDeviceToHost, task->stream),
 					  "recv redo list");
 			REQ_CHECK(hipStreamSynchronize(task->stream), "fold (partitions)");
@@ -1965,7 +1884,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 	REQ_CHECK(hipMemcpyAsync(stage_status, d_kg + offsetof(kern_gpupreagg, status), sizeof(cl_int),
 							 hipMemcpyDeviceToHost, task->stream),
 			  "recv status");
-	REQ_CHECK(hipMemcpyAsync(stage_status + 16, sess->htab, 16, hipMemcpyDeviceToHost, task->stream),
+	REQ_CHECK(hipMemcpyAsync(stage_status + 16, sess->htab, HASH_HEAD_COUNTERS, hipMemcpyDeviceToHost, task->stream),
 			  "recv table head");
 	task->pfm.num_dma_recv += 2;
 	task->pfm.bytes_dma_recv += sizeof(cl_int) + 16;
@@ -1973,9 +1892,9 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 	task->finish = [stage_status, sess, req, second](strom_task_impl *t)
 	{
 		cl_int	status;
-		cl_uint	words[4];
+		gpupreagg_hash_head head;
 		memcpy(&status, stage_status, sizeof(status));
-		memcpy(words, stage_status + 16, sizeof(words));
+		memcpy(&head, stage_status + 16, HASH_HEAD_COUNTERS);
 		if (status == StromError_SumRangeUnproven && !second)
 		{
 			/* the running bound of the integer sums reached 2^63 and nothing was folded:
@@ -1999,9 +1918,9 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 		}
 		if (status == StromError_SumRangeUnproven)
 			status = StromError_CpuReCheck;
-		if (status == StromError_Success && words[3] != 0)
+		if (status == StromError_Success && head.overflow != 0)
 			status = StromError_DataStoreNoSpace;	/* cannot happen: headroom is kept for every claim */
-		sess->groups_known = std::max<cl_uint>(sess->groups_known, words[2]);
+		sess->groups_known = std::max<cl_uint>(sess->groups_known, head.ngroups);
 		t->errcode = status;
 	};
 	task_enqueue(task);
@@ -2082,7 +2001,7 @@ gpupreagg_session_new(strom_devprog_key key,
 				sess->pack_attno.assign(sess->agg_resno.size(), 0);
 				sess->packable = false;
 			}
-			if (sess->agg_resno.size() > 32)
+			if (sess->agg_resno.size() > GPUPREAGG_PACK_MAXAGGS)
 				sess->packable = false;
 		}
 		else
@@ -2294,7 +2213,7 @@ strom_gpupreagg_table_layout(strom_gpupreagg *sess, int resno, size_t *p_bits_of
 	}
 	int a = (int)(std::find(sess->agg_resno.begin(), sess->agg_resno.end(), resno) - sess->agg_resno.begin());
 	*p_bits_off = 0;			/* flags word: bit 0 seen, bit 1+a has-value */
-	*p_vals_off = sess->table_offset(1 + a, sess->ctl.ngroups);
+	*p_vals_off = gpupreagg_table_offset(1 + a, sess->ctl.ngroups);
 	return 0;
 }
 
@@ -2396,7 +2315,7 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 	*p_errcode = 0;
 	strom_task_impl *jtask = static_cast<strom_task_impl *>(join_handle);
 	if (!sess || sess->hashed || !sess->has_domain || (!lookup && !jtask) || !tbl || !outer ||
-		ncols < 1 || ncols > 64 || !src_depth || !src_colidx || !type_oids)
+		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids)
 	{
 		*p_errcode = StromError_BadRequestMessage;
 		return nullptr;
@@ -2433,8 +2352,8 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 		return nullptr;
 	}
 	const kern_data_store *oh = (const kern_data_store *)ohead.data();
-	auto	img = std::make_shared<std::vector<char>>(sizeof(joined_map_image), 0);
-	joined_map_image *jm = (joined_map_image *)img->data();
+	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_joined_map), 0);
+	gpupreagg_joined_map *jm = (gpupreagg_joined_map *)img->data();
 	jm->ncols = ncols;
 	jm->key_col = key_attno - 1;
 	jm->key_attlen = oh->colmeta[key_attno - 1].attlen;
@@ -2477,15 +2396,16 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 	}
 	{
 		/* one packed record per slot: presence, NULL bits and the wanted inner columns */
-		int		cols[16], lens[16], which[16], ints[16], n = 0;
-		unsigned offs[16], reclen = 0;
+		const int MAXCOLS = HASHJOIN_DIMREC_MAXCOLS;
+		int		cols[MAXCOLS], lens[MAXCOLS], which[MAXCOLS], ints[MAXCOLS], n = 0;
+		unsigned offs[MAXCOLS], reclen = 0;
 		void   *recs = nullptr;
 		dimrec_narrow nw;
 		for (int i = 0; i < ncols; i++)
 		{
 			if (src_depth[i] != 1)
 				continue;
-			if (n == 16)
+			if (n == MAXCOLS)
 			{
 				*p_errcode = StromError_BadRequestMessage;
 				return nullptr;
@@ -2513,17 +2433,17 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 		}
 		jm->recs = (cl_ulong)(uintptr_t)recs;
 		jm->reclen = reclen;
-		if (lookup && nw.reclen != 0)
+		if (lookup && nw.spec.reclen != 0)
 		{
 			jm->recs = (cl_ulong)(uintptr_t)nw.recs;
-			jm->reclen = nw.reclen;
+			jm->reclen = nw.spec.reclen;
 			jm->narrow = 1;
 			for (int k = 0; k < n; k++)
 			{
 				jm->c[which[k]].dimvalues = 0;
-				jm->nshift[which[k]] = nw.shift[k];
-				jm->nmask[which[k]] = nw.mask[k];
-				jm->nmin[which[k]] = nw.vmin[k];
+				jm->nshift[which[k]] = nw.spec.shift[k];
+				jm->nmask[which[k]] = nw.spec.mask[k];
+				jm->nmin[which[k]] = nw.spec.vmin[k];
 			}
 		}
 	}
@@ -2697,7 +2617,7 @@ strom_gpupreagg_compact(strom_gpupreagg *sess, const uint32_t *bitmap, size_t nw
 	if (!sess || !sess->has_domain || sess->nfolds != 0 || !sess->table_owned || sess->ctl.remap != 0)
 		return StromError_BadRequestMessage;
 	Device *dev = sess->dev;
-	dense_ctl &ctl = sess->ctl;
+	gpupreagg_dense_ctl &ctl = sess->ctl;
 	size_t	words = ((size_t)ctl.dense_ngroups + 31) / 32;
 	std::vector<cl_uint> bits(words, 0);
 	std::lock_guard<std::mutex> g(sess->lock);
@@ -2768,7 +2688,7 @@ strom::gpupreagg_hash_export_device(strom_gpupreagg *sess, char **p_recs, cl_uin
 									cl_ulong *p_sum_bound)
 {
 	Device *dev = sess->dev;
-	size_t	reclen = 8 + 8 * (sess->key_resno.size() + sess->agg_resno.size());
+	size_t	reclen = GPUPREAGG_EXPORT_RECLEN(sess->key_resno.size(), sess->agg_resno.size());
 	cl_uint	ngroups = 0, overflow = 0;
 	std::lock_guard<std::mutex> g(sess->lock);
 
@@ -2826,7 +2746,7 @@ strom::gpupreagg_hash_export_parts_device(strom_gpupreagg *sess, cl_uint nparts,
 										  size_t *p_reclen, cl_ulong *p_sum_bound)
 {
 	Device *dev = sess->dev;
-	size_t	reclen = 8 + 8 * (sess->key_resno.size() + sess->agg_resno.size());
+	size_t	reclen = GPUPREAGG_EXPORT_RECLEN(sess->key_resno.size(), sess->agg_resno.size());
 	cl_uint	ngroups = 0, overflow = 0;
 	std::lock_guard<std::mutex> g(sess->lock);
 
@@ -3006,7 +2926,7 @@ strom::gpupreagg_hash_import_device(strom_gpupreagg *sess, const char *d_recs, c
 int
 strom::gpupreagg_get_merge_plan(strom_gpupreagg *sess, gpupreagg_merge_plan *plan)
 {
-	if (!sess || sess->hashed || !sess->has_domain || !sess->table || sess->agg_resno.size() > 31 ||
+	if (!sess || sess->hashed || !sess->has_domain || !sess->table || sess->agg_resno.size() > PREAGG_MERGE_MAXAGGS ||
 		sess->numeric_aggs)				/* (64-bit numerics do not add up with ncclSum: gather the partial rows) */
 		return StromError_BadRequestMessage;
 	memset(&plan->spec, 0, sizeof(plan->spec));
@@ -3026,7 +2946,7 @@ strom::gpupreagg_get_merge_plan(strom_gpupreagg *sess, gpupreagg_merge_plan *pla
 			default:					return StromError_BadRequestMessage;
 		}
 		plan->spec.op[a] = op;
-		plan->spec.vals_off[a] = sess->table_offset(1 + (int)a, sess->ctl.ngroups);
+		plan->spec.vals_off[a] = gpupreagg_table_offset(1 + (int)a, sess->ctl.ngroups);
 		if (sess->is_intsum((int)a))
 		{
 			/* 128 bits wide in the table: travels as three carry-free limbs (strom_merge.h) */
@@ -3054,7 +2974,7 @@ strom::gpupreagg_sessions_mergeable(strom_gpupreagg *dst, strom_gpupreagg *src)
 	if (dst->hashed)
 		return true;
 	/* dense tables: slot i must be the same group in both */
-	const dense_ctl &a = dst->ctl, &b = src->ctl;
+	const gpupreagg_dense_ctl &a = dst->ctl, &b = src->ctl;
 	if (!dst->has_domain || !src->has_domain || a.ngroups != b.ngroups || a.nkeys != b.nkeys ||
 		a.dense_ngroups != b.dense_ngroups || dst->present != src->present)
 		return false;
@@ -3289,7 +3209,7 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 	Device *dev = sess->dev;
 	int		ncols = (int)sess->targets.size();
 	size_t	nkeys = sess->key_resno.size(), naggs = sess->agg_resno.size();
-	size_t	reclen = 8 + 8 * (nkeys + naggs);
+	size_t	reclen = GPUPREAGG_EXPORT_RECLEN(nkeys, naggs);
 	cl_uint	ngroups = 0, overflow = 0;
 	std::vector<char> recs;
 	std::lock_guard<std::mutex> g(sess->lock);
@@ -3407,9 +3327,9 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 	std::vector<spill> spills;
 	for (cl_uint r = 0; r < ngroups; r++)
 	{
-		const char *rec = recs.data() + reclen * r;
-		cl_uint		flags = ((const cl_uint *)rec)[1];
-		const cl_ulong *vals = (const cl_ulong *)(rec + 8) + nkeys;
+		const gpupreagg_export_rec *rec = (const gpupreagg_export_rec *)(recs.data() + reclen * r);
+		cl_uint		flags = rec->flags;
+		const cl_ulong *vals = rec->body + nkeys;
 		for (size_t a = 0; a < naggs; a++)
 		{
 			const strom_preagg_target &t = sess->targets[sess->agg_resno[a]];
@@ -3432,10 +3352,10 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 	if (destlen < need)
 		return -StromError_DataStoreNoSpace;
 	fetch_init_head(sess, dest, need, nrows_out);
-	auto put_keys = [&](const char *rec, Datum *values, cl_char *isnull)
+	auto put_keys = [&](const gpupreagg_export_rec *rec, Datum *values, cl_char *isnull)
 	{
-		cl_uint		knull = ((const cl_uint *)rec)[0];
-		const cl_ulong *kimg = (const cl_ulong *)(rec + 8);
+		cl_uint		knull = rec->knull;
+		const cl_ulong *kimg = rec->body;
 		for (size_t k = 0; k < nkeys; k++)
 		{
 			int		resno = sess->key_resno[k];
@@ -3456,9 +3376,9 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 	cl_uint	row = 0;
 	for (cl_uint r = 0; r < ngroups; r++, row++)
 	{
-		const char *rec = recs.data() + reclen * r;
-		cl_uint		flags = ((const cl_uint *)rec)[1];
-		const cl_ulong *vals = (const cl_ulong *)(rec + 8) + nkeys;
+		const gpupreagg_export_rec *rec = (const gpupreagg_export_rec *)(recs.data() + reclen * r);
+		cl_uint		flags = rec->flags;
+		const cl_ulong *vals = rec->body + nkeys;
 		Datum	   *values = KERN_DATA_STORE_VALUES(dest, row);
 		cl_char	   *isnull = KERN_DATA_STORE_ISNULL(dest, row);
 		memset(values, 0, KDS_TUPSLOT_STRIDE(ncols));
@@ -3492,7 +3412,7 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 		memset(values, 0, KDS_TUPSLOT_STRIDE(ncols));
 		for (int i = 0; i < ncols; i++)
 			isnull[i] = (sess->targets[i].kind != STROM_PREAGG_NROWS);	/* nrows = 0 */
-		put_keys(recs.data() + reclen * sp.rec, values, isnull);
+		put_keys((const gpupreagg_export_rec *)(recs.data() + reclen * sp.rec), values, isnull);
 		isnull[sp.resno] = 0;
 		values[sp.resno] = sp.image;
 		row++;
@@ -3502,18 +3422,6 @@ gpupreagg_fetch_hashed(strom_gpupreagg *sess, kern_data_store *dest, size_t dest
 }
 
 }	/* namespace */
-
-/* mirrors preagg_export_spec of devlib/strom_merge.h */
-struct export_spec {
-	cl_uint		ngroups, ncols, stride, nkeys;
-	cl_long		key_min[8];
-	cl_uint		key_range[8];
-	cl_uint		key_stride[8];
-	struct {
-		cl_uint		kind, len, which, float4;
-		cl_ulong	vals_off, hi_off;
-	} col[64];
-};
 
 /*
  * dense sessions: the partial rows formatted on the device (preagg_dense_export_rows) and copied
@@ -3528,7 +3436,7 @@ gpupreagg_fetch_dense_device(strom_gpupreagg *sess, kern_data_store *dest, size_
 	cl_uint		N = sess->ctl.ngroups;
 
 	*p_fallback = true;
-	if (!sess->present.empty() || ncols > 64 || sess->key_resno.size() > 8 || getenv("STROM_GPUPREAGG_FETCH_ON_HOST"))
+	if (!sess->present.empty() || ncols > PREAGG_EXPORT_MAXCOLS || sess->key_resno.size() > GPUPREAGG_MAXKEYS || getenv("STROM_GPUPREAGG_FETCH_ON_HOST"))
 		return 0;
 	for (const strom_preagg_target &t : sess->targets)
 		if (t.type_oid == STROM_NUMERICOID && t.kind != STROM_PREAGG_NROWS)
@@ -3543,7 +3451,7 @@ gpupreagg_fetch_dense_device(strom_gpupreagg *sess, kern_data_store *dest, size_
 	(void)hipSetDevice(dev->hip_id);
 	if (!sess->d_export_spec)
 	{
-		export_spec	spec;
+		preagg_export_spec	spec;
 		memset(&spec, 0, sizeof(spec));
 		spec.ngroups = N;
 		spec.ncols = (cl_uint)ncols;
@@ -3565,7 +3473,7 @@ gpupreagg_fetch_dense_device(strom_gpupreagg *sess, kern_data_store *dest, size_
 			auto &c = spec.col[sess->agg_resno[a]];
 			bool	isfloat = type_is_float(t.type_oid);
 			c.which = 1 + (cl_uint)a;
-			c.vals_off = sess->table_offset(1 + (int)a, N);
+			c.vals_off = gpupreagg_table_offset(1 + (int)a, N);
 			c.len = (cl_uint)(t.kind == STROM_PREAGG_NROWS ? 8 : type_length(t.type_oid));
 			c.float4 = (t.type_oid == STROM_FLOAT4OID);
 			if (t.kind == STROM_PREAGG_NROWS)
@@ -3680,7 +3588,7 @@ strom_gpupreagg_fetch(strom_gpupreagg *sess, kern_data_store *dest, size_t destl
 			const strom_preagg_target &t = sess->targets[sess->agg_resno[a]];
 			if (!sess->is_intsum((int)a) || !(gflags[g] & (2u << a)))
 				continue;
-			cl_ulong lo = ((const cl_ulong *)(host.data() + sess->table_offset(1 + (int)a, N)))[g];
+			cl_ulong lo = ((const cl_ulong *)(host.data() + gpupreagg_table_offset(1 + (int)a, N)))[g];
 			cl_long	 hi = ((const cl_long *)(host.data() + sess->table_hi_offset((int)a, N)))[g];
 			int		rc = sum_pieces(t, lo, hi, pieces);
 			if (rc != 0)
@@ -3738,7 +3646,7 @@ strom_gpupreagg_fetch(strom_gpupreagg *sess, kern_data_store *dest, size_t destl
 		{
 			int		resno = sess->agg_resno[a];
 			const strom_preagg_target &t = sess->targets[resno];
-			const cl_ulong *vals = (const cl_ulong *)(host.data() + sess->table_offset(1 + (int)a, N));
+			const cl_ulong *vals = (const cl_ulong *)(host.data() + gpupreagg_table_offset(1 + (int)a, N));
 			if (t.kind == STROM_PREAGG_NROWS)
 				values[resno] = vals[g];
 			else if (!(gflags[g] & (2u << a)))
@@ -3825,15 +3733,6 @@ strom_gpupreagg_fetch(strom_gpupreagg *sess, kern_data_store *dest, size_t destl
  * ================================================================== */
 namespace {
 
-/* host image of gpupreagg_keyrange_t (strom_gpupreagg.h) */
-struct keyrange_image {
-	cl_long		kmin[STROM_PREAGG_MAXKEYS];
-	cl_long		kmax[STROM_PREAGG_MAXKEYS];
-	cl_uint		nvalues[STROM_PREAGG_MAXKEYS];
-	cl_uint		nrows;
-	cl_uint		pad;
-};
-
 int
 chunk_domain(strom_devprog_key key, Program *prog, Device *dev,
 			 const strom_preagg_target *targets, int ntargets,
@@ -3910,7 +3809,7 @@ chunk_domain(strom_devprog_key key, Program *prog, Device *dev,
 	hipFunction_t fn = prog->get_function(dev, "gpupreagg_keyrange", &errcode);
 	if (!fn)
 		return errcode;
-	keyrange_image img;
+	gpupreagg_keyrange_t img;
 	memset(&img, 0, sizeof(img));
 	for (int k = 0; k < STROM_PREAGG_MAXKEYS; k++)
 	{

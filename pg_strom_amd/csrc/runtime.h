@@ -29,6 +29,9 @@ extern "C" hipError_t hipExtModuleLaunchKernel(hipFunction_t f, uint32_t globalW
 #include <vector>
 
 #include "strom_hip.h"
+#include "devlib/strom_ctl.h"		/* the control blocks written for the kernels: one definition with the device */
+
+static_assert(GPUPREAGG_MAXKEYS == STROM_PREAGG_MAXKEYS, "the ABI's key bound is the kernels' key bound");
 
 namespace strom {
 
@@ -225,13 +228,10 @@ void		task_wait_completed(strom_task_impl *task);
 Device	   *get_device(int dindex);
 /* gpuhashjoin.cpp, for consumers of join results (gpupreagg.cpp) */
 int			hashjoin_table_dimcol(strom_hashjoin_table *tbl, int col, int attlen, void **p_values, void **p_isnull);
-/* narrow form of the slot records (strom_hashjoin.h): reclen 2 or 4, or 0 = not available */
+/* narrow form of the slot records (strom_hashjoin.h): spec.reclen 2 or 4, or 0 = not available */
 struct dimrec_narrow {
-	unsigned	reclen = 0;
 	void	   *recs = nullptr;
-	cl_uint		shift[16] = {};
-	cl_uint		mask[16] = {};
-	cl_long		vmin[16] = {};
+	hashjoin_dimrec_narrow_spec spec = {};
 };
 /* narrowable (n flags, may be NULL): column i holds integers (not float bits); narrow (may be
  * NULL) receives the narrow records when every column is narrowable and the fields fit 32 bits */
@@ -240,19 +240,9 @@ int			hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols, 
 								   const int *narrowable = nullptr, dimrec_narrow *narrow = nullptr);
 int			hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 									   int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual = nullptr);
-/* gpupreagg.cpp, for the RCCL merge (parallel.cpp): mirrors preagg_merge_spec of
- * devlib/strom_merge.h */
+/* gpupreagg.cpp, for the RCCL merge (parallel.cpp) */
 struct gpupreagg_merge_plan {
-	struct {
-		cl_uint		ngroups;
-		cl_uint		naggs;
-		cl_uint		op[31];
-		cl_uint		__pad;
-		cl_ulong	vals_off[31];
-		cl_ulong	hi_off[31];
-		cl_uint		mid_idx[31];
-		cl_uint		__pad2;
-	} spec;
+	preagg_merge_spec spec;
 	char	   *table;
 	size_t		table_bytes;
 	cl_uint		nmid;				/* integer sums: lanes of ngroups words the merge needs as scratch */

@@ -675,10 +675,4 @@ strom_locate_tuple(const kern_data_store *kds, cl_int format, cl_uint rowidx)
 	return NULL;
 }
 
-/* needs a 'cl_int errcode' in scope, like the pg_<T>_vref() calls it replaces */
-#define STROM_TUPLE_REF(NAME, kds, htup, colidx)									\
-	(((htup) != NULL && (cl_uint)(colidx) < (kds)->ncols)							\
-	 ? pg_##NAME##_tupref(&errcode, (kds)->colmeta, htup, colidx)					\
-	 : pg_##NAME##_make(0, true))
-
 #endif	/* STROM_COMMON_DEVICE_H */

@@ -96,6 +96,7 @@ STROM_DEFINE_KVARS_FROM_COLUMN
 		KV_.__dummy = 0;					\
 		STROM_KFIXED_LIST(STROM_KFIXED_FILL_ONE)	\
 	} while (0)
+#include "strom_rowreader.h"	/* the reader of the any-format kernels */
 
 STROM_DEVICE pg_bool_t
 gpupreagg_qual_eval(cl_int *errcode, const strom_kparams &KP, const strom_kvars &KV);
@@ -455,11 +456,31 @@ gpupreagg_sum_magnitude(cl_long v)
 #ifndef GPUPREAGG_COUNTALL_FIRST
 #define GPUPREAGG_COUNTALL_FIRST	(-1)
 #endif
+/* GPUPREAGG_SUMBITS_<a>: 0 no integer sum, 1..63 a static bound, 64..66 none -- the code generator emits
+ * nothing else, and a new value must be given its place here: with rowflags 0 (the hashed GROUP BY's
+ * check passes) this is "SUMBITS >= 64" */
+static_assert(true
+#define X(aidx,resno,OP,NAME)	&& GPUPREAGG_SUMBITS_##aidx >= 0 && GPUPREAGG_SUMBITS_##aidx <= 66
+			  GPUPREAGG_AGG_LIST(X)
+#undef X
+			  , "GPUPREAGG_SUMBITS_<a> beyond 66: say in GPUPREAGG_MEASURE_SUM whether it is measured");
 #define GPUPREAGG_MEASURE_SUM(aidx, rowflags)	\
 	(GPUPREAGG_SUMBITS_##aidx == 64 ||		\
 	 ((GPUPREAGG_SUMBITS_##aidx == 65 || GPUPREAGG_SUMBITS_##aidx == 66) && !((rowflags) & ROWFLAG_ZONE_BOUNDED)))
 #define GPUPREAGG_COUNT_IS_ALIASED(aidx, rowflags)	\
 	(GPUPREAGG_COUNTALL_##aidx && (aidx) != GPUPREAGG_COUNTALL_FIRST && ((rowflags) & ROWFLAG_ALL_NOTNULL))
+
+/*
+ * an integer sum without a static bound (measure: GPUPREAGG_MEASURE_SUM of the aggregate): OR the
+ * magnitude of this row's input into summag.  Compiled away for every other aggregate.
+ */
+template <int OP, typename T>
+STROM_DEVICE void
+gpupreagg_measure_intsum(cl_ulong &summag, bool measure, const T &av)
+{
+	if (gpupreagg_is_intsum<OP, decltype(av.value)>::value && measure)
+		summag |= (av.isnull ? 0UL : gpupreagg_sum_magnitude((cl_long)av.value));
+}
 
 STROM_DEVICE void
 gpupreagg_writeback_summag(kern_gpupreagg *kgpreagg, cl_ulong summag)
@@ -780,9 +801,8 @@ gpupreagg_dense_row(char *lds, const gpupreagg_dense_ctl *ctl, const gpupreagg_l
 	cl_uint		need = GPUPREAGG_FLAG_SEEN;
 
 #define X(aidx,resno,OP,NAME)														\
-	/* an integer sum without a static bound: measure (see "integer sums never wrap") */	\
-	if (gpupreagg_is_intsum<GPUPREAGG_OP_##OP, pg_##NAME##_base_t>::value && GPUPREAGG_MEASURE_SUM(aidx, rowflags))	\
-		summag |= (av_##aidx.isnull ? 0UL : gpupreagg_sum_magnitude((cl_long)av_##aidx.value));	\
+	/* (see "integer sums never wrap") */											\
+	gpupreagg_measure_intsum<GPUPREAGG_OP_##OP>(summag, GPUPREAGG_MEASURE_SUM(aidx, rowflags), av_##aidx);	\
 	if (!(GPUPREAGG_OP_##OP == GPUPREAGG_OP_NROWS && GPUPREAGG_COUNT_IS_ALIASED(aidx, rowflags)))	\
 		need |= gpupreagg_lds_accum<GPUPREAGG_OP_##OP, aidx>(lds, L.vals_off[aidx], slot, av_##aidx, chunk_status);
 	GPUPREAGG_AGG_LIST(X)
@@ -1273,8 +1293,7 @@ gpupreagg_dense_generic_body(kern_gpupreagg *kgpreagg,
 	char *lds)
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	cl_uint		nrows = (use_map ? (cl_uint)krowmap->nvalids : kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
 	cl_uint		nsplits = ctl->nsplits;
 	cl_uint		G = ctl->groups_per_split;
 	cl_uint		NREP = ctl->nrep;
@@ -1293,38 +1312,14 @@ gpupreagg_dense_generic_body(kern_gpupreagg *kgpreagg,
 	gpupreagg_remap_init(ctl);
 	gpupreagg_lds_layout_init(L, G, NREP);
 	gpupreagg_lds_init(lds, L, G, NREP);
-	/* COLUMN chunk (row map, census): column pointers hoisted, no chunk
-	 * header field is read per row */
-	const bool	is_column = IS_COLUMN;		/* fixed per launch */
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	for (size_t r = (size_t)wg_in_split * GPUPREAGG_BLOCK + threadIdx.x;
-		 r < nrows;
+		 r < rr_nrows;
 		 r += (size_t)wgs_per_split * GPUPREAGG_BLOCK)
 	{
-		cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
 		strom_kvars	KV;
 		cl_int		errcode = param_error;
-		const HeapTupleHeaderData *htup = NULL;
-		if (!is_column && row_family)
-			htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = (is_column											\
-			? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-			: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-			: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-		STROM_KVAR_LIST(X)
-#undef X
-		if (is_column)
-			strom_kvars_from_column(KV, kds, &errcode);
-		STROM_KVARS_FINISH(KV);
+		STROM_ROW_LOAD_ROW(KV, errcode, STROM_ROW_INDEX(r));
 		gpupreagg_dense_row(lds, ctl, L, KP, KV, gid_lo, G, NREP, rep, errcode, &chunk_status, summag, 0u);
 	}
 	gpupreagg_store_slab(lds, L, slabs + (size_t)blockIdx.x * ctl->slab_bytes, G, NREP, &chunk_status);
@@ -2516,6 +2511,22 @@ STROM_DEVICE cl_ulong strom_key_image(cl_double v)
 }
 STROM_DEVICE cl_ulong strom_key_image(cl_float v)	{ return strom_key_image((cl_double)v); }
 
+/* the GROUP BY keys of a row: their images, and bit k of knull for a NULL key k */
+STROM_DEVICE void
+gpupreagg_key_images(const strom_kparams &KP, const strom_kvars &KV, cl_int *errcode,
+					 cl_ulong *kimg, cl_uint &knull)
+{
+	knull = 0;
+#define X(kidx,resno,NAME)															\
+	{																				\
+		pg_##NAME##_t kv = gpupreagg_key_##kidx(errcode, KP, KV);					\
+		kimg[kidx] = (kv.isnull ? 0UL : strom_key_image(kv.value));					\
+		knull |= (kv.isnull ? (1u << kidx) : 0u);									\
+	}
+	GPUPREAGG_KEY_LIST(X)
+#undef X
+}
+
 /* 32-bit multiplies only: a 64-bit product is four quarter-rate VALU operations
  * on gfx950, and with hash roles every row is hashed once per role */
 STROM_DEVICE cl_uint
@@ -2734,8 +2745,8 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
 	gpupreagg_hash_head *head = (gpupreagg_hash_head *)htab;
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	cl_uint		nrows = (use_map ? (cl_uint)krowmap->nvalids : kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
+	const cl_uint nrows = rr_nrows;
 	cl_int		chunk_status = StromError_Success;
 	cl_ulong	summag = 0;			/* OR of the integer sums' input magnitudes */
 	cl_int		param_error = StromError_Success;
@@ -2765,16 +2776,7 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 			T.state[i] = 0;
 		__syncthreads();
 	}
-	const bool	is_column = IS_COLUMN;
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	/*
 	 * one row, its columns loaded: qual, keys, partial inputs, then into the
 	 * work-group's LDS table or, without room there, the global one
@@ -2782,7 +2784,7 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 	auto fold_loaded = [&](const strom_kvars &KV, cl_int errcode, cl_uint kds_index, size_t pos)
 	{
 		cl_ulong	kimg[GPUPREAGG_NKEYS + 1];
-		cl_uint		knull = 0;
+		cl_uint		knull;
 		pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
 		if (errcode == StromError_Success && !EVAL(rc))
 		{
@@ -2790,14 +2792,7 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 				rolemap[pos] = GPUPREAGG_ROLE_NONE;		/* filtered: no role folds it */
 			return;
 		}
-#define X(kidx,resno,NAME)															\
-		{																			\
-			pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);				\
-			kimg[kidx] = (kv.isnull ? 0UL : strom_key_image(kv.value));				\
-			knull |= (kv.isnull ? (1u << kidx) : 0u);								\
-		}
-		GPUPREAGG_KEY_LIST(X)
-#undef X
+		gpupreagg_key_images(KP, KV, &errcode, kimg, knull);
 #define X(aidx,resno,OP,NAME)														\
 		pg_##NAME##_t av_##aidx = gpupreagg_agg_##aidx(&errcode, KP, KV);
 		GPUPREAGG_AGG_LIST(X)
@@ -2811,8 +2806,7 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 		{
 			/* integer sums without a static bound: the check pass measures their inputs */
 #define X(aidx,resno,OP,NAME)														\
-			if (gpupreagg_is_intsum<GPUPREAGG_OP_##OP, pg_##NAME##_base_t>::value && GPUPREAGG_SUMBITS_##aidx >= 64)	\
-				summag |= (av_##aidx.isnull ? 0UL : gpupreagg_sum_magnitude((cl_long)av_##aidx.value));
+			gpupreagg_measure_intsum<GPUPREAGG_OP_##OP>(summag, GPUPREAGG_MEASURE_SUM(aidx, 0u), av_##aidx);
 			GPUPREAGG_AGG_LIST(X)
 #undef X
 			/* the check pass has the row's hash at hand: leave its role (6 bits: up to 64
@@ -2914,17 +2908,13 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 		bool		active = (strom_lane_id() < nready);
 		cl_uint		kds_index = queue[(qhead + (active ? strom_lane_id() : 0)) & (GPUPREAGG_HASH_QUEUE - 1)];
 		strom_kvars	KV;
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = STROM_COLUMN_REF_CACHED(NAME, col_##attno, nul_##attno, kds_index);
-		STROM_KVAR_LIST_GROUPING(X)
-#undef X
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index);
-		STROM_KVAR_LIST_REST(X)
-#undef X
+		cl_int		errcode = param_error;
+		/* (the scan's other roles read the grouping columns too; nobody else reads the rest) */
+		STROM_ROW_LOAD(STROM_KVAR_LIST_GROUPING, CACHED, KV, errcode, kds_index);
+		STROM_ROW_LOAD(STROM_KVAR_LIST_REST, NT, KV, errcode, kds_index);
 		STROM_KVARS_FINISH(KV);
 		if (active)
-			fold_loaded(KV, param_error, kds_index, 0);
+			fold_loaded(KV, errcode, kds_index, 0);
 		qhead += nready;
 	};
 	/*
@@ -2990,26 +2980,16 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 			live[j] = (r < nrows);
 			if (!live[j])
 				r = 0;					/* nrows > 0 here: a harmless row, ignored below */
-			cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
+			cl_uint		kds_index = STROM_ROW_INDEX(r);
 			cl_int		errcode = param_error;
-			const HeapTupleHeaderData *htup = NULL;
-			if (!is_column && row_family)
-				htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-			KVs[j].KVAR_##attno = (is_column									\
-				? (ROLES ? STROM_COLUMN_REF_CACHED(NAME, col_##attno, nul_##attno, kds_index)	\
-						 : STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index))	\
-				: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)			\
-				: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-			STROM_KVAR_LIST_GROUPING(X)
 			if (!ROLES)
+				STROM_ROW_LOAD_ROW(KVs[j], errcode, kds_index);
+			else
 			{
-				STROM_KVAR_LIST_REST(X)
+				/* the scan: what the qual and the keys read, through the caches (drain() reads the rest) */
+				STROM_ROW_LOAD(STROM_KVAR_LIST_GROUPING, CACHED, KVs[j], errcode, kds_index);
+				STROM_KVARS_FINISH(KVs[j]);
 			}
-#undef X
-			if (is_column && !ROLES)
-				strom_kvars_from_column(KVs[j], kds, &errcode);
-			STROM_KVARS_FINISH(KVs[j]);
 			errs[j] = errcode;
 			kidx[j] = kds_index;
 		}
@@ -3032,15 +3012,8 @@ gpupreagg_hash_body(kern_gpupreagg *kgpreagg,
 				if (!(errcode == StromError_Success && !EVAL(rc)))
 				{
 					cl_ulong	kimg[GPUPREAGG_NKEYS + 1];
-					cl_uint		knull = 0;
-#define X(kidx,resno,NAME)															\
-					{																\
-						pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KVs[j]);	\
-						kimg[kidx] = (kv.isnull ? 0UL : strom_key_image(kv.value));	\
-						knull |= (kv.isnull ? (1u << kidx) : 0u);					\
-					}
-					GPUPREAGG_KEY_LIST(X)
-#undef X
+					cl_uint		knull;
+					gpupreagg_key_images(KP, KVs[j], &errcode, kimg, knull);
 					own = (errcode != StromError_Success ||
 						   ((gpupreagg_hash_of(kimg, knull) >> 7) & (nroles - 1)) == role);
 				}
@@ -3269,8 +3242,8 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 						  const gpupreagg_part_ctl *ctl, cl_uint *lds_words, cl_uint lds_rows = 0)
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	cl_uint		nrows = (use_map ? (cl_uint)krowmap->nvalids : kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
+	const cl_uint nrows = rr_nrows;
 	cl_int		chunk_status = StromError_Success;
 	cl_ulong	summag = 0;			/* OR of the integer sums' input magnitudes */
 	cl_int		param_error = StromError_Success;
@@ -3281,46 +3254,11 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 	if (MODE != 0 && kgpreagg->status != StromError_Success)
 		return;							/* the check pass sends the chunk back */
 	gpupreagg_load_kparams(KP, kparams, &param_error);
-	const bool	is_column = IS_COLUMN;
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	auto load_row = [&](size_t r, strom_kvars &KV, cl_int &errcode)
 	{
-		cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
-		const HeapTupleHeaderData *htup = NULL;
 		errcode = param_error;
-		if (!is_column && row_family)
-			htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = (is_column											\
-			? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-			: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-			: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-		STROM_KVAR_LIST(X)
-#undef X
-		if (is_column)
-			strom_kvars_from_column(KV, kds, &errcode);
-		STROM_KVARS_FINISH(KV);
-	};
-	/* keys of a row -> images; false when an expression failed */
-	auto eval_keys = [&](const strom_kvars &KV, cl_int &errcode, cl_ulong *kimg, cl_uint &knull)
-	{
-		knull = 0;
-#define X(kidx,resno,NAME)															\
-		{																			\
-			pg_##NAME##_t kv = gpupreagg_key_##kidx(&errcode, KP, KV);				\
-			kimg[kidx] = (kv.isnull ? 0UL : strom_key_image(kv.value));				\
-			knull |= (kv.isnull ? (1u << kidx) : 0u);								\
-		}
-		GPUPREAGG_KEY_LIST(X)
-#undef X
+		STROM_ROW_LOAD_ROW(KV, errcode, STROM_ROW_INDEX(r));
 	};
 
 	if (MODE == 0)
@@ -3357,7 +3295,7 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 				pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KVs[j]);
 				if (errcode != StromError_Success || EVAL(rc))
 				{
-					eval_keys(KVs[j], errcode, kimg, knull);
+					gpupreagg_key_images(KP, KVs[j], &errcode, kimg, knull);
 #define X(aidx,resno,OP,NAME)														\
 					pg_##NAME##_t av_##aidx = gpupreagg_agg_##aidx(&errcode, KP, KVs[j]);
 					GPUPREAGG_AGG_LIST(X)
@@ -3367,8 +3305,7 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 					else
 					{
 #define X(aidx,resno,OP,NAME)														\
-						if (gpupreagg_is_intsum<GPUPREAGG_OP_##OP, pg_##NAME##_base_t>::value && GPUPREAGG_SUMBITS_##aidx >= 64)	\
-							summag |= (av_##aidx.isnull ? 0UL : gpupreagg_sum_magnitude((cl_long)av_##aidx.value));
+						gpupreagg_measure_intsum<GPUPREAGG_OP_##OP>(summag, GPUPREAGG_MEASURE_SUM(aidx, 0u), av_##aidx);
 						GPUPREAGG_AGG_LIST(X)
 #undef X
 						part = (gpupreagg_hash_of(kimg, knull) >> pshift) & (nparts - 1);
@@ -3494,7 +3431,7 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 				cl_uint		abits = 0;
 				cl_ulong	rec[GPUPREAGG_REC_WORDS];
 				int			vp = 1 + GPUPREAGG_NKEYS;
-				eval_keys(KVs[j], errcode, kimg, knull);
+				gpupreagg_key_images(KP, KVs[j], &errcode, kimg, knull);
 				for (int k = 0; k < GPUPREAGG_NKEYS; k++)
 					rec[1 + k] = kimg[k];
 #define X(aidx,resno,OP,NAME)														\
@@ -3607,7 +3544,7 @@ gpupreagg_hash_parts_body(kern_gpupreagg *kgpreagg,
 				cl_ulong	kimg[GPUPREAGG_NKEYS + 1];
 				cl_uint		knull;
 				cl_uint		abits = 0;
-				eval_keys(KVs[j], errcode, kimg, knull);
+				gpupreagg_key_images(KP, KVs[j], &errcode, kimg, knull);
 				cl_uint		rank = __hip_atomic_fetch_add(&lcount[part[j]], 1u, __ATOMIC_RELAXED,
 														  __HIP_MEMORY_SCOPE_WORKGROUP);
 				cl_ulong   *dst = records + (size_t)(lbase[part[j]] + rank) * GPUPREAGG_REC_WORDS;
@@ -4414,45 +4351,20 @@ gpupreagg_census_body(const kern_gpupreagg *kgpreagg, const kern_data_store *kds
 				 const gpupreagg_dense_ctl *ctl, cl_uint *bitmap)
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	size_t		nrows = (use_map ? (size_t)krowmap->nvalids : (size_t)kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
 	cl_int		param_error = StromError_Success;
 	strom_kparams KP;
 
 	gpupreagg_load_kparams(KP, kparams, &param_error);
-	/* COLUMN chunk (row map, census): column pointers hoisted, no chunk
-	 * header field is read per row */
-	const bool	is_column = IS_COLUMN;		/* fixed per launch */
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-		 r < nrows;
+		 r < rr_nrows;
 		 r += (size_t)gridDim.x * blockDim.x)
 	{
-		cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
 		strom_kvars	KV;
 		cl_int		errcode = param_error;
 		cl_uint		gid;
-		const HeapTupleHeaderData *htup = NULL;
-		if (!is_column && row_family)
-			htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = (is_column											\
-			? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-			: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-			: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-		STROM_KVAR_LIST(X)
-#undef X
-		if (is_column)
-			strom_kvars_from_column(KV, kds, &errcode);
-		STROM_KVARS_FINISH(KV);
+		STROM_ROW_LOAD_ROW(KV, errcode, STROM_ROW_INDEX(r));
 		pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
 		if (errcode == StromError_Success && !EVAL(rc))
 			continue;
@@ -4499,22 +4411,12 @@ gpupreagg_keyrange_body(const kern_gpupreagg *kgpreagg, const kern_data_store *k
 						gpupreagg_keyrange_t *out)
 {
 	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	size_t		nrows = (use_map ? (size_t)krowmap->nvalids : (size_t)kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
 	cl_int		param_error = StromError_Success;
 	strom_kparams KP;
 
 	gpupreagg_load_kparams(KP, kparams, &param_error);
-	const bool	is_column = IS_COLUMN;
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	cl_long		my_min[GPUPREAGG_NKEYS > 0 ? GPUPREAGG_NKEYS : 1];
 	cl_long		my_max[GPUPREAGG_NKEYS > 0 ? GPUPREAGG_NKEYS : 1];
 	cl_uint		my_seen = 0;			/* bit k: key k had a value; bit 31: a row passed */
@@ -4524,25 +4426,12 @@ gpupreagg_keyrange_body(const kern_gpupreagg *kgpreagg, const kern_data_store *k
 		my_max[k] = -0x7fffffffffffffffL - 1;
 	}
 	for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-		 r < nrows;
+		 r < rr_nrows;
 		 r += (size_t)gridDim.x * blockDim.x)
 	{
-		cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : (cl_uint)r);
 		strom_kvars	KV;
 		cl_int		errcode = param_error;
-		const HeapTupleHeaderData *htup = NULL;
-		if (!is_column && row_family)
-			htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-		KV.KVAR_##attno = (is_column											\
-			? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-			: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-			: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-		STROM_KVAR_LIST(X)
-#undef X
-		if (is_column)
-			strom_kvars_from_column(KV, kds, &errcode);
-		STROM_KVARS_FINISH(KV);
+		STROM_ROW_LOAD_ROW(KV, errcode, STROM_ROW_INDEX(r));
 		pg_bool_t	rc = gpupreagg_qual_eval(&errcode, KP, KV);
 		if (errcode == StromError_Success && !EVAL(rc))
 			continue;

@@ -69,6 +69,8 @@ struct strom_kvars {
 #define STROM_KVARLENA_LIST(X)
 #endif
 STROM_DEFINE_KVARS_FROM_COLUMN
+#define STROM_KVARS_FINISH(KV)	((KV).__dummy = 0)
+#include "strom_rowreader.h"	/* the reader of the any-format kernel */
 
 STROM_DEVICE pg_bool_t
 gpuscan_qual_eval(cl_int *errcode,
@@ -452,8 +454,9 @@ gpuscan_qual_generic_body(kern_gpuscan *kgpuscan,
 {
 	const kern_parambuf *kparams = KERN_GPUSCAN_PARAMBUF(kgpuscan);
 	kern_resultbuf *kresults = KERN_GPUSCAN_RESULTBUF(kgpuscan);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	cl_uint		nrows = (use_map ? (cl_uint)krowmap->nvalids : kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
+	const bool	use_map = rr_use_map;
+	const cl_uint nrows = rr_nrows;
 	cl_uint		ntiles = (nrows + GPUSCAN_TILE_ROWS - 1) / GPUSCAN_TILE_ROWS;
 	cl_int		chunk_error = StromError_Success;
 	cl_int		param_error = StromError_Success;
@@ -461,19 +464,8 @@ gpuscan_qual_generic_body(kern_gpuscan *kgpuscan,
 	strom_kparams KP;
 
 	gpuscan_load_kparams(KP, kparams, &param_error);
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 
-	/* COLUMN chunk behind a row map: column pointers hoisted, no chunk
-	 * header field is read per row */
-	const bool	is_column = IS_COLUMN;		/* fixed per launch: the other accessor is not compiled in */
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir_g = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir_g[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir_g[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir_g[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
 	for (cl_uint tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
 	{
 		cl_uint		tile_base = tile * GPUSCAN_TILE_ROWS;
@@ -500,22 +492,9 @@ gpuscan_qual_generic_body(kern_gpuscan *kgpuscan,
 				st[k][j] = 0;
 				if (r < nrows)
 				{
-					cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : r);
 					strom_kvars	KV;
 					cl_int		errcode = param_error;
-					const HeapTupleHeaderData *htup = NULL;
-					if (!is_column && row_family)
-						htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = (is_column											\
-						? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-						: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-						: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-					STROM_KVAR_LIST(X)
-#undef X
-					KV.__dummy = 0;
-					if (is_column)
-						strom_kvars_from_column(KV, kds, &errcode);
+					STROM_ROW_LOAD_ROW(KV, errcode, STROM_ROW_INDEX(r));
 					pg_bool_t rc = gpuscan_qual_eval(&errcode, KP, KV);
 					st[k][j] = gpuscan_row_status(rc, errcode, &chunk_error);
 				}

@@ -84,6 +84,8 @@ struct strom_kvars {
 #define STROM_KVARLENA_LIST(X)
 #endif
 STROM_DEFINE_KVARS_FROM_COLUMN
+#define STROM_KVARS_FINISH(KV)	((KV).__dummy = 0)
+#include "strom_rowreader.h"	/* the reader of the general kernel */
 
 /* canonical 64-bit image of a key value: equal values <=> equal images */
 STROM_DEVICE cl_ulong hashjoin_key_image(cl_bool v)		{ return (cl_ulong)(v != 0); }
@@ -491,8 +493,8 @@ gpuhashjoin_main_body(kern_hashjoin *__restrict__ khashjoin,
 {
 	const kern_parambuf *kparams = KERN_HASHJOIN_PARAMBUF(khashjoin);
 	kern_resultbuf *kresults = KERN_HASHJOIN_RESULTBUF(khashjoin);
-	bool		use_map = (krowmap != NULL && krowmap->nvalids >= 0);
-	cl_uint		nrows = (use_map ? (cl_uint)krowmap->nvalids : kds->nitems);
+	STROM_ROW_READER_MAP(kds, krowmap);
+	const cl_uint nrows = rr_nrows;
 	/*
 	 * rows per thread and tile: up to HASHJOIN_GENERIC_ROWS, but no more than it takes to give every
 	 * work-group of the launch a tile -- a thread walks its rows one after the other through chains
@@ -512,17 +514,7 @@ gpuhashjoin_main_body(kern_hashjoin *__restrict__ khashjoin,
 	strom_kparams KP;
 
 	hashjoin_load_kparams(KP, kparams, &param_error);
-	/* COLUMN chunk: column pointers hoisted, no header reads per row */
-	const bool	is_column = IS_COLUMN;	/* compile-time: the other accessor is not even compiled in */
-	const cl_int chunk_format = kds->format;
-	const bool	row_family = (chunk_format == KDS_FORMAT_ROW || chunk_format == KDS_FORMAT_ROW_FLAT);
-	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
-#define X(attno,colidx,NAME)													\
-	const char *col_##attno = (is_column ? (const char *)kds + coldir[colidx].values_off : NULL);	\
-	const cl_uint *nul_##attno = ((is_column && coldir[colidx].nulls_off != 0)	\
-		? (const cl_uint *)((const char *)kds + coldir[colidx].nulls_off) : NULL);
-	STROM_KVAR_LIST(X)
-#undef X
+	STROM_ROW_READER(IS_COLUMN, kds, ktoast);		/* fixed per launch (strom_rowreader.h) */
 	if (nrels != kmhash->ntables + 1 || nrels != HASHJOIN_NRELS + 1)
 	{
 		/* uniform: every thread leaves (opencl_hashjoin.h:305-309) */
@@ -574,23 +566,11 @@ gpuhashjoin_main_body(kern_hashjoin *__restrict__ khashjoin,
 				cl_uint	r = tile * tile_rows + j * HASHJOIN_BLOCK + threadIdx.x;
 				if (r < nrows)
 				{
-					cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : r);
+					cl_uint		kds_index = STROM_ROW_INDEX(r);
 					cl_int		errcode = param_error;
 					cl_uint		n;
 					strom_kvars	KV;
-					const HeapTupleHeaderData *htup = NULL;
-					if (!is_column && row_family)
-						htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = (is_column											\
-						? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-						: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-						: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-					STROM_KVAR_LIST(X)
-#undef X
-					KV.__dummy = 0;
-					if (is_column)
-						strom_kvars_from_column(KV, kds, &errcode);
+					STROM_ROW_LOAD_ROW(KV, errcode, kds_index);
 #if (defined(HASHJOIN_ABLATE) && HASHJOIN_ABLATE != 0) && !defined(STROM_DIAGNOSTIC_BUILD)
 #error "HASHJOIN_ABLATE builds leave work out and give wrong results: measurement only (set STROM_DIAGNOSTIC_BUILD=1, as scripts/gpu_*_ablate* do)"
 #endif
@@ -660,7 +640,7 @@ gpuhashjoin_main_body(kern_hashjoin *__restrict__ khashjoin,
 				{
 					/* the count pass's one match, from the scratch */
 					cl_uint		r = tile * tile_rows + j * HASHJOIN_BLOCK + threadIdx.x;
-					cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : r);
+					cl_uint		kds_index = STROM_ROW_INDEX(r);
 					out[0] = (cl_int)(kds_index + 1);
 #pragma unroll
 					for (int d = 0; d < HASHJOIN_NRELS; d++)
@@ -670,22 +650,10 @@ gpuhashjoin_main_body(kern_hashjoin *__restrict__ khashjoin,
 				else if ((emit_mask >> j) & 1)
 				{
 					cl_uint		r = tile * tile_rows + j * HASHJOIN_BLOCK + threadIdx.x;
-					cl_uint		kds_index = (use_map ? (cl_uint)krowmap->rindex[r] : r);
+					cl_uint		kds_index = STROM_ROW_INDEX(r);
 					cl_int		errcode = param_error;
 					strom_kvars	KV;
-					const HeapTupleHeaderData *htup = NULL;
-					if (!is_column && row_family)
-						htup = strom_locate_tuple(kds, chunk_format, kds_index);
-#define X(attno,colidx,NAME)													\
-					KV.KVAR_##attno = (is_column											\
-						? STROM_COLUMN_REF(NAME, col_##attno, nul_##attno, kds_index)		\
-						: row_family ? STROM_TUPLE_REF(NAME, kds, htup, colidx)				\
-						: pg_##NAME##_vref(kds, ktoast, &errcode, colidx, kds_index));
-					STROM_KVAR_LIST(X)
-#undef X
-					KV.__dummy = 0;
-					if (is_column)
-						strom_kvars_from_column(KV, kds, &errcode);
+					STROM_ROW_LOAD_ROW(KV, errcode, kds_index);
 					out += (size_t)nrels *
 						gpuhashjoin_execute<ALL_SINGLE>(&errcode, KP, KV, kmhash, hjidx, kds_index, out);
 				}

@@ -69,7 +69,14 @@ typedef struct {
 	cl_uint		num_kern_sort;
 	cl_ulong	time_kern_prep;
 	cl_ulong	time_kern_sort;
-	/* extension: kernel time in nanoseconds (HIP events resolve < 1us) */
+	/* extension: kernel time in nanoseconds (HIP events resolve < 1us).
+	 * GpuScan over a resident COLUMN chunk (gpuscan_qual_column_resident): consecutive such
+	 * scans of a device run on two streams and overlap at their boundary, so the time of
+	 * scan N is EXCLUSIVE of the device's previous resident scan P:
+	 *     end(N) - max(begin(N), end(P)),  kept within [0, end(N) - begin(N)]
+	 * With one scan stream (STROM_GPUSCAN_SCAN_STREAMS=1), or with nothing to overlap, that
+	 * is end(N) - begin(N).  Summed over a run of scans it is the span the device was busy
+	 * with them: bytes / time stays a bandwidth.  time_kern_exec is the same in microseconds. */
 	cl_ulong	time_kern_exec_ns;
 	cl_ulong	time_kern_prep_ns;
 	cl_ulong	time_kern_proj_ns;

@@ -60,9 +60,20 @@ gpuscan_geometry(Device *dev, hipFunction_t fn, uint32_t nrows, size_t *p_grid, 
 	size_t	tile_rows = (size_t)block * 4 * quads;
 	size_t	ntiles = (nrows + tile_rows - 1) / tile_rows;
 	int		per_cu = 0;
-	if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess
-		|| per_cu < 1)
-		per_cu = 1;
+	{
+		/* asked once per (function, block), not at every launch */
+		std::lock_guard<std::mutex> g(dev->occupancy_lock);
+		auto	it = dev->occupancy.find({fn, block});
+		if (it != dev->occupancy.end())
+			per_cu = it->second;
+		else
+		{
+			if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0) != hipSuccess
+				|| per_cu < 1)
+				per_cu = 1;
+			dev->occupancy[{fn, block}] = per_cu;
+		}
+	}
 	if (const char *v = getenv("STROM_GPUSCAN_BLOCKS_PER_CU"))
 		per_cu = std::max(1, atoi(v));
 	size_t	grid = (size_t)dev->prop.multiProcessorCount * per_cu;
@@ -151,6 +162,14 @@ gpuscan_launch_resident(strom_task_impl *task, Program *prog, const gpuscan_requ
 	int			block;
 	gpuscan_geometry(dev, fn, req.nrows, &grid, &block);
 	void	   *params[] = { &args };
+	/*
+	 * This scan takes the other scan stream than the device's previous one, so that its
+	 * work-groups follow the previous scan's CU by CU instead of waiting at the queue for
+	 * its last one.  The turn, the launch and the hand-over to the completer are one step
+	 * (Device::scan_streams).
+	 */
+	std::lock_guard<std::mutex> turn(dev->scan_submit_lock);
+	task->stream = dev->scan_streams[dev->scan_turn++ % dev->num_scan_streams];
 	if (use_ext_launch())
 	{
 		hipEvent_t	ev_begin = (task->pfm.enabled ? task_event_slot(task) : nullptr);	/* ev[0] */
@@ -218,11 +237,13 @@ gpuscan_launch(strom_task_impl *task, Program *prog, gpuscan_request req)
 	}
 	task->pfm.time_kern_build = (cl_ulong)prog->build_usec;
 	/*
-	 * A resident chunk needs no bulk DMA, so nothing is gained by letting
-	 * two bandwidth-bound kernels share the chip: such requests run in
-	 * order on stream 0 (their event pairs then time the kernel alone).
-	 * Requests that upload their chunk rotate over the other streams so
-	 * that the next chunk's DMA overlaps this chunk's kernel.
+	 * A resident chunk needs no bulk DMA: on the copied path such requests run in
+	 * order on stream 0.  Those that take gpuscan_launch_resident pick their stream
+	 * there: two consecutive ones sit on two streams, and since a CU has room for the
+	 * work-groups of one scan only, the next scan fills the CUs as the running one
+	 * leaves them (its kernel time is reported exclusive of the running one's,
+	 * strom_perfmon.time_kern_exec_ns).  Requests that upload their chunk rotate over
+	 * the other streams so that the next chunk's DMA overlaps this chunk's kernel.
 	 */
 	if (req.kds_dev || dev->streams.size() < 2)
 		task->stream = dev->streams[0];

@@ -556,6 +556,60 @@ strom_task *strom_submit_gpupreagg_mapped(strom_gpupreagg *sess, strom_dstore *k
 										  strom_done_cb done, void *arg, int *p_errcode);
 
 /* ------------------------------------------------------------------ *
+ * GROUP BY text / character(n): a key dictionary in front of GpuPreAgg
+ *
+ * The reference's keycomp takes any type with a comparison function, bpchar
+ * and text included (gpupreagg_codegen_keycomp, gpupreagg.c:1208-1242); its
+ * partial rows then carry the key datums themselves.  GpuPreAgg here groups by
+ * fixed-width key images, so a varlena key column is first replaced by dense
+ * int4 ids under a device-resident dictionary (devlib/strom_textdict.h):
+ * GpuPreAgg groups the ENCODED chunk by (key (var K int4)) -- the id column's
+ * zone map {0, num_keys-1} is the domain of a dense session, and
+ * strom_submit_gpupreagg_chunk takes an encoded chunk as it is -- and the
+ * caller replaces ids by key datums after the fetch.
+ *
+ * One encode at a time per dictionary: the caller serialises, as with a
+ * session.  An encode that ends in an error leaves every dictionary usable;
+ * keys it had inserted before the error (an earlier key column of the same
+ * call) may remain as ids no row was folded under.  They are harmless: a
+ * result only carries ids that rows were folded under.
+ * Refused with StromError_BadRequestMessage before any launch: a NULL handle,
+ * a source that is not a resident COLUMN chunk, a key column whose attlen is
+ * not -1, a varlena carry column, nkeys outside 1..STROM_PREAGG_MAXKEYS, a
+ * dictionary of another device than the chunk's.
+ * ------------------------------------------------------------------ */
+typedef struct strom_textdict strom_textdict;
+/* stands in for the varlena case of gpupreagg_codegen_keycomp: the dictionary decides which
+ * keys are equal (bytewise; character(n) without its trailing blanks).
+ * type_oid: STROM_TEXTOID | STROM_BPCHARNOID */
+strom_textdict *strom_textdict_create(int type_oid, uint32_t nkeys_hint, int dindex, int *p_errcode);
+uint32_t	strom_textdict_num_keys(strom_textdict *dict);
+/* keycomp's varlena case, per chunk: a new resident COLUMN chunk, same rows in the same order as src:
+ *   columns 0..nkeys-1 : int4 ids of src column key_colidx[i] under dicts[i]; NULL where the key is
+ *                        NULL (notnull bitmap as src's); zone map {0, num_keys-1}, KDS_COLSTAT_MINMAX
+ *   then               : copies of the fixed-width by-value src columns carry_colidx[], with their
+ *                        colmeta, notnull bitmaps and zone maps
+ * Blocks until the chunk is ready.  A compressed or external key datum: StromError_CpuReCheck,
+ * the chunk is the CPU's and the dictionaries are as before the call. */
+strom_dstore *strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, int nkeys,
+									strom_dstore *src, const int32_t *carry_colidx, int ncarry,
+									int *p_errcode);
+/* stands in for pg_fixup_tupslot_varlena (the way varlena keys of a partial row reach the host):
+ * the keys by id -- heap image + offsets[id] of each complete datum in it; returns the number of
+ * keys (negative: -errcode), *p_heap_bytes the heap's size; sizes alone when heap_out == NULL */
+long		strom_textdict_fetch(strom_textdict *dict, void *heap_out, size_t heaplen,
+								 uint64_t *offsets_out, size_t noffsets, size_t *p_heap_bytes);
+/* device time of the last encode's kernels under this dictionary, when strom_set_perfmon(1):
+ * ns_out[4] = probe, settle, emit, rebuild (measurement; no counterpart in the reference) */
+int			strom_textdict_kernel_ns(strom_textdict *dict, uint64_t *ns_out);
+/* the device program the last encode under this dictionary ran (0: none yet): its text carries the
+ * TEXTDICT_BLOCK / TEXTDICT_HASH_BITS in force (strom_get_devprog_source) */
+strom_devprog_key strom_textdict_program(strom_textdict *dict);
+/* forget every key (keycomp keeps no state between queries; this is the next query's dictionary) */
+void		strom_textdict_reset(strom_textdict *dict);
+void		strom_textdict_release(strom_textdict *dict);
+
+/* ------------------------------------------------------------------ *
  * multi-GPU: merge of the per-GPU GpuPreAgg tables over RCCL (xGMI)
  *
  * The reference has no collective (SURVEY.md section 2.3 / section 5

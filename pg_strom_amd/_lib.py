@@ -187,6 +187,16 @@ PROTOTYPES = {
                                                    c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "strom_submit_gpupreagg_mapped": (c_void_p, [c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "strom_textdict_create": (c_void_p, [c_int, c_uint32, c_int, ctypes.POINTER(c_int)]),
+    "strom_textdict_num_keys": (c_uint32, [c_void_p]),
+    "strom_textdict_encode": (c_void_p, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int32), c_int, c_void_p,
+                                         ctypes.POINTER(c_int32), c_int, ctypes.POINTER(c_int)]),
+    "strom_textdict_fetch": (ctypes.c_long, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                             ctypes.POINTER(c_size_t)]),
+    "strom_textdict_kernel_ns": (c_int, [c_void_p, ctypes.POINTER(c_uint64)]),
+    "strom_textdict_program": (c_uint64, [c_void_p]),
+    "strom_textdict_reset": (None, [c_void_p]),
+    "strom_textdict_release": (None, [c_void_p]),
     "strom_task_wait": (c_int, [c_void_p, ctypes.POINTER(strom_perfmon)]),
     "strom_task_release": (None, [c_void_p]),
     "strom_task_devptr": (c_void_p, [c_void_p]),

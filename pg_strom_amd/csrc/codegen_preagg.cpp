@@ -467,8 +467,9 @@ strom_codegen_gpupreagg(const char *spec, strom_codegen_result *out,
 			const devtype_info *dt = devtype_lookup(tg.type_oid);
 			/* a partial row carries by-value datums only (TUPSLOT, 8 bytes per column):
 			 * text / character(n) may be compared in quals and arguments, not grouped or
-			 * aggregated (the reference's keycomp / aggcalc catalogues have no varlena
-			 * entry either, gpupreagg.c:1181-1440) */
+			 * aggregated HERE.  The reference's keycomp does take bpchar and text keys
+			 * (gpupreagg.c:1208-1242); in this build they arrive as int4 ids of a key
+			 * dictionary that runs in front of GpuPreAgg (strom_textdict_*, strom_hip.h) */
 			if (dt->type_flags & DEVTYPE_IS_VARLENA)
 				codegen_error("GpuPreAgg target of type %s: group keys and partial aggregates "
 							  "are fixed-width", dt->sql_name);

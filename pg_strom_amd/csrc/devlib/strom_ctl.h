@@ -373,4 +373,51 @@ static_assert(sizeof(hashjoin_dimrec_spec) == 264, "hashjoin_dimrec_spec");
 static_assert(sizeof(hashjoin_dimrec_range) == 320, "hashjoin_dimrec_range");
 static_assert(sizeof(hashjoin_dimrec_narrow_spec) == 264, "hashjoin_dimrec_narrow_spec");
 
+/* ---------------------------------------------------------------------- *
+ * text key dictionary (strom_textdict.h, textdict.cpp)
+ * ---------------------------------------------------------------------- */
+/* the words one encode call exchanges with the host: zeroed before every probe */
+struct textdict_ctl {
+	cl_int		status;				/* probe: worst row error, NoSpace included */
+	cl_uint		nnew;				/* probe: keys claimed by this call */
+	cl_uint		nnull;				/* probe: rows whose key is NULL */
+	cl_uint		toofull;			/* probe: the claims took the table past half full (a word of its own:
+									 * 'status' keeps the row errors' priority) */
+	cl_ulong	heap_need;			/* probe: bytes of the new keys' datums, each rounded up to 4 */
+	cl_ulong	heap_cursor;		/* settle: bytes handed out so far, on top of heap_usage */
+};
+/* entries[id]: where key 'id' lies in the dictionary heap, and its (masked) hash */
+struct textdict_entry {
+	cl_ulong	hash;
+	cl_ulong	off;
+};
+/* newkeys[k]: the slot a probe claimed and the row of this chunk whose datum it stands for */
+struct textdict_newkey {
+	cl_uint		slot;
+	cl_uint		row;
+};
+/* the kernels' argument (device addresses as cl_ulong: one layout for both compilers) */
+struct textdict_args {
+	cl_ulong	slots;				/* cl_ulong[nslots] */
+	cl_ulong	entries;			/* textdict_entry[>= nkeys + nnew] */
+	cl_ulong	heap;				/* char[heap_size] */
+	cl_ulong	ctl;				/* textdict_ctl */
+	cl_ulong	row_slot;			/* cl_uint[nrows]: the row's slot, ~0 = NULL or failed row */
+	cl_ulong	newkeys;			/* textdict_newkey[nrows] */
+	cl_ulong	heap_usage;			/* bytes of the heap in use before this call */
+	cl_ulong	heap_size;
+	cl_ulong	out_values;			/* emit: cl_int[nrows] of the encoded chunk */
+	cl_ulong	out_notnull;		/* emit: its notnull bitmap */
+	cl_uint		nslots;				/* power of two */
+	cl_uint		nkeys;				/* keys before this call; rebuild: all keys */
+	cl_uint		nnew;				/* settle */
+	cl_uint		colidx;				/* the key column of the source chunk */
+	cl_uint		blank_padded;		/* character(n): trailing blanks do not count */
+	cl_uint		__pad;
+};
+static_assert(sizeof(textdict_ctl) == 32, "textdict_ctl");
+static_assert(sizeof(textdict_entry) == 16, "textdict_entry");
+static_assert(sizeof(textdict_newkey) == 8, "textdict_newkey");
+static_assert(sizeof(textdict_args) == 104, "textdict_args");
+
 #endif	/* STROM_CTL_H */

@@ -115,32 +115,7 @@ STROM_DEVICE cl_ulong hashjoin_key_image(cl_float v)	{ return hashjoin_key_image
 STROM_DEVICE cl_ulong
 hashjoin_varlena_image(cl_ulong datum, bool blank_padded)
 {
-	cl_int		len;
-	const cl_uchar *p = strom_varlena_payload(datum, &len);
-	cl_ulong	h = 0xcbf29ce484222325UL ^ (cl_ulong)0;
-	cl_int		i = 0;
-
-	if (blank_padded)
-		while (len > 0 && p[len - 1] == ' ')
-			len--;
-	/* eight bytes a step (strom_load_u64), the tail gathered into one last word */
-	for (; i + 8 <= len; i += 8)
-	{
-		h = (h ^ strom_load_u64(p + i)) * 0x9e3779b97f4a7c15UL;
-		h ^= h >> 29;
-	}
-	cl_ulong	tail = (cl_ulong)(cl_uint)len << 56;
-	if (i < len && len >= 8)
-	{
-		/* the last (len - i) bytes out of one overlapping load of the string's last eight */
-		tail ^= strom_load_u64(p + len - 8) >> (8 * (8 - (len - i)));
-		i = len;
-	}
-	for (int sh = 0; i < len; i++, sh += 8)
-		tail ^= (cl_ulong)p[i] << sh;
-	h = (h ^ tail) * 0xbf58476d1ce4e5b9UL;
-	h ^= h >> 31;
-	return h;
+	return strom_varlena_hash(datum, blank_padded);		/* strom_textlib.h: shared with the key dictionary */
 }
 #endif
 

@@ -170,6 +170,44 @@ strom_bytes_equal(const cl_uchar *s1, cl_int len1, const cl_uchar *s2, cl_int le
 	return true;
 }
 
+/*
+ * 64-bit mix of a datum's payload, eight bytes a step, the tail gathered into one last word: equal
+ * strings have equal hashes, NOT the other way round -- whoever uses it compares the bytes of every
+ * candidate (the text-key join: texteq / bpchareq on the HASH index, strom_hashjoin.h; the key
+ * dictionary: strom_bytes_equal, strom_textdict.h).  blank_padded: character(n), trailing blanks do
+ * not count (bpchar_truelen, opencl_textlib.h:154-166).
+ */
+STROM_DEVICE cl_ulong
+strom_varlena_hash(cl_ulong datum, bool blank_padded)
+{
+	cl_int		len;
+	const cl_uchar *p = strom_varlena_payload(datum, &len);
+	cl_ulong	h = 0xcbf29ce484222325UL ^ (cl_ulong)0;
+	cl_int		i = 0;
+
+	if (blank_padded)
+		while (len > 0 && p[len - 1] == ' ')
+			len--;
+	/* eight bytes a step (strom_load_u64), the tail gathered into one last word */
+	for (; i + 8 <= len; i += 8)
+	{
+		h = (h ^ strom_load_u64(p + i)) * 0x9e3779b97f4a7c15UL;
+		h ^= h >> 29;
+	}
+	cl_ulong	tail = (cl_ulong)(cl_uint)len << 56;
+	if (i < len && len >= 8)
+	{
+		/* the last (len - i) bytes out of one overlapping load of the string's last eight */
+		tail ^= strom_load_u64(p + len - 8) >> (8 * (8 - (len - i)));
+		i = len;
+	}
+	for (int sh = 0; i < len; i++, sh += 8)
+		tail ^= (cl_ulong)p[i] << sh;
+	h = (h ^ tail) * 0xbf58476d1ce4e5b9UL;
+	h ^= h >> 31;
+	return h;
+}
+
 STROM_DEVICE cl_int
 strom_text_compare(cl_ulong a, cl_ulong b)
 {

@@ -1,0 +1,677 @@
+/*
+ * textdict.cpp -- text / character(n) group keys as dense int4 ids (devlib/strom_textdict.h)
+ *
+ * The reference's keycomp compares varlena keys through their type's comparison function
+ * (gpupreagg_codegen_keycomp, gpupreagg.c:1208-1242).  Here the keys of a resident COLUMN chunk
+ * are replaced by their ids in a device-resident dictionary BEFORE GpuPreAgg sees the chunk; the
+ * encoded chunk groups by (key (var K int4)) on the dense path, its zone map {0, num_keys-1}
+ * being the domain.  The ids are turned back into datums after the fetch (strom_textdict_fetch).
+ *
+ * One encode, per key column:
+ *   probe -> read {status, nnew, nnull, heap_need} (the one small copy) ->
+ *     NoSpace (no place found, or the claims took the table past half full), heap or entries short:
+ *                                      grow, rebuild, probe again (the probe is idempotent for
+ *                                      the keys that have entries; claims are dropped by the rebuild)
+ *     another error:                   rebuild at the same size, return it: the dictionary is as before
+ *     else:                            settle, emit, rebuild larger if the load passed 1/2
+ */
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "runtime.h"
+
+using namespace strom;
+
+struct strom_textdict {
+	int			type_oid = 0;
+	int			dindex = 0;
+	bool		blank_padded = false;
+	cl_uint		nkeys = 0;
+	cl_uint		nslots = 0;
+	cl_uint		entries_cap = 0;
+	size_t		heap_size = 0, heap_usage = 0;
+	cl_ulong   *slots = nullptr;
+	textdict_entry *entries = nullptr;
+	char	   *heap = nullptr;
+	textdict_ctl *ctl = nullptr;
+	cl_uint		nkeys_hint = 0;
+	/* device time of the last encode's kernels, when the perfmon is on: probe, settle, emit, rebuild */
+	uint64_t	kern_ns[4] = {0, 0, 0, 0};
+	/* the program the last encode ran: TEXTDICT_BLOCK / TEXTDICT_HASH_BITS are part of its text */
+	strom_devprog_key program = 0;
+};
+
+namespace {
+
+enum { K_PROBE = 0, K_SETTLE, K_EMIT, K_REBUILD };
+
+/* the fixed program; the two knobs are part of its text (as build() pre-builds it) */
+std::string
+textdict_source(void)
+{
+	std::string s;
+	for (const char *name : {"TEXTDICT_BLOCK", "TEXTDICT_HASH_BITS"})
+	{
+		const char *v = getenv((std::string("STROM_") + name).c_str());
+		if (v && *v)
+			s += std::string("#define ") + name + " " + std::to_string(atoi(v)) + "\n";
+	}
+	return s + "#include \"strom_kds.h\"\n#include \"strom_common.h\"\n#include \"strom_textlib.h\"\n"
+		"#include \"strom_textdict.h\"\n";
+}
+
+unsigned
+textdict_block(void)
+{
+	const char *v = getenv("STROM_TEXTDICT_BLOCK");
+	int		b = (v && *v) ? atoi(v) : 256;
+	return (b >= 64 && b <= 1024 && b % 64 == 0) ? (unsigned)b : 0;	/* 0: the program does not build either */
+}
+
+Program *
+textdict_program(int *p_errcode, strom_devprog_key *p_key)
+{
+	/* one reference per variant is kept for the life of the process */
+	static std::mutex &lock = *new std::mutex();
+	static std::map<std::string, strom_devprog_key> &keys = *new std::map<std::string, strom_devprog_key>();
+	std::string src = textdict_source();
+	strom_devprog_key key;
+	{
+		std::lock_guard<std::mutex> g(lock);
+		auto it = keys.find(src);
+		if (it == keys.end())
+			it = keys.emplace(src, strom_get_devprog_key(src.c_str(), 0)).first;
+		key = it->second;
+	}
+	*p_key = key;
+	if (textdict_block() == 0 || strom_lookup_device_program(key, 1) != STROM_DEVPROG_READY)
+	{
+		*p_errcode = StromError_ProgramBuildFailure;
+		return nullptr;
+	}
+	return lookup_program(key);
+}
+
+cl_uint
+pow2_at_least(size_t n)
+{
+	size_t	p = 16;
+	while (p < n && p < ((size_t)1 << 31))
+		p <<= 1;
+	return (cl_uint)p;
+}
+
+struct Encoder {
+	Device	   *dev;
+	hipStream_t	stream;
+	hipFunction_t fn[4];
+	unsigned	block;
+	unsigned	max_grid;
+	bool		timed;
+
+	unsigned grid_for(size_t n) const
+	{
+		return (unsigned)std::max<size_t>(1, std::min<size_t>((n + block - 1) / block, max_grid));
+	}
+
+	int launch(strom_textdict *dict, int which, unsigned grid, void **args)
+	{
+		hipEvent_t	ev0 = nullptr, ev1 = nullptr;
+		if (timed && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess))
+			return StromError_HipInternal;
+		if (timed)
+			(void)hipEventRecord(ev0, stream);
+		hipError_t	rc = hipModuleLaunchKernel(fn[which], grid, 1, 1, block, 1, 1, 0, stream, args, nullptr);
+		if (timed)
+		{
+			float	ms = 0;
+			(void)hipEventRecord(ev1, stream);
+			if (rc == hipSuccess && hipEventSynchronize(ev1) == hipSuccess &&
+				hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
+				dict->kern_ns[which] += (uint64_t)((double)ms * 1e6);
+			(void)hipEventDestroy(ev0);
+			(void)hipEventDestroy(ev1);
+		}
+		return rc == hipSuccess ? 0 : hip_errcode(rc, "textdict kernel");
+	}
+
+	textdict_args base_args(strom_textdict *dict) const
+	{
+		textdict_args a;
+		memset(&a, 0, sizeof(a));
+		a.slots = (cl_ulong)(uintptr_t)dict->slots;
+		a.entries = (cl_ulong)(uintptr_t)dict->entries;
+		a.heap = (cl_ulong)(uintptr_t)dict->heap;
+		a.ctl = (cl_ulong)(uintptr_t)dict->ctl;
+		a.heap_usage = dict->heap_usage;
+		a.heap_size = dict->heap_size;
+		a.nslots = dict->nslots;
+		a.nkeys = dict->nkeys;
+		a.blank_padded = dict->blank_padded ? 1 : 0;
+		return a;
+	}
+
+	int read_ctl(strom_textdict *dict, textdict_ctl *out)
+	{
+		if (hipMemcpyAsync(out, dict->ctl, sizeof(*out), hipMemcpyDeviceToHost, stream) != hipSuccess ||
+			hipStreamSynchronize(stream) != hipSuccess)
+			return StromError_HipInternal;
+		return 0;
+	}
+
+	/* entries -> a cleared slot array of 'nslots' words (the dictionary's own when the size stays) */
+	int rebuild(strom_textdict *dict, cl_uint nslots)
+	{
+		if (nslots != dict->nslots || !dict->slots)
+		{
+			cl_ulong   *fresh = (cl_ulong *)dev->pool.alloc(sizeof(cl_ulong) * (size_t)nslots);
+			if (!fresh)
+				return StromError_OutOfMemory;
+			/* the old array may still be read by a queued kernel: the stream is in order, and the
+			 * pool hands memory out again only to work queued later or synchronised with */
+			if (hipStreamSynchronize(stream) != hipSuccess)
+			{
+				dev->pool.release(fresh);
+				return StromError_HipInternal;
+			}
+			if (dict->slots)
+				dev->pool.release(dict->slots);
+			dict->slots = fresh;
+			dict->nslots = nslots;
+		}
+		if (hipMemsetAsync(dict->slots, 0, sizeof(cl_ulong) * (size_t)dict->nslots, stream) != hipSuccess ||
+			hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), stream) != hipSuccess)
+			return StromError_HipInternal;
+		if (dict->nkeys == 0)
+			return 0;
+		textdict_args a = base_args(dict);
+		void	   *args[] = { &a };
+		int			rc = launch(dict, K_REBUILD, grid_for(dict->nkeys), args);
+		textdict_ctl ctl;
+		if (rc == 0)
+			rc = read_ctl(dict, &ctl);
+		if (rc == 0 && ctl.status != 0)
+			rc = ctl.status;
+		return rc;
+	}
+
+	/* room for 'need' bytes / entries, what is there copied over */
+	template <typename T>
+	int grow(T **p_buf, size_t used, size_t need)
+	{
+		T	   *fresh = (T *)dev->pool.alloc(sizeof(T) * need);
+		if (!fresh)
+			return StromError_OutOfMemory;
+		if ((used > 0 && hipMemcpyAsync(fresh, *p_buf, sizeof(T) * used, hipMemcpyDeviceToDevice, stream) != hipSuccess) ||
+			hipStreamSynchronize(stream) != hipSuccess)
+		{
+			dev->pool.release(fresh);
+			return StromError_HipInternal;
+		}
+		if (*p_buf)
+			dev->pool.release(*p_buf);
+		*p_buf = fresh;
+		return 0;
+	}
+
+	/* one key column: ids into out_values / out_notnull; *p_nnull = its NULL rows */
+	int encode_column(strom_textdict *dict, strom_dstore *src, cl_uint colidx, cl_uint *row_slot,
+					  textdict_newkey *newkeys, void *out_values, void *out_notnull, cl_uint *p_nnull)
+	{
+		const void *a_src = src->devptr;
+		cl_uint		nrows = src->head.nitems;
+		textdict_ctl ctl;
+		int			rc;
+
+		for (int turn = 0; ; turn++)
+		{
+			textdict_args a = base_args(dict);
+			a.row_slot = (cl_ulong)(uintptr_t)row_slot;
+			a.newkeys = (cl_ulong)(uintptr_t)newkeys;
+			a.colidx = colidx;
+			void	   *args[] = { &a_src, &a };
+
+			if (hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), stream) != hipSuccess)
+				return StromError_HipInternal;
+			if ((rc = launch(dict, K_PROBE, grid_for(nrows), args)) != 0 || (rc = read_ctl(dict, &ctl)) != 0)
+				return rc;
+			size_t	keys_after = (size_t)dict->nkeys + ctl.nnew;
+			/* no place found, or the claims took the table past half full; a row error goes first */
+			bool	nospace = (ctl.status == StromError_DataStoreNoSpace || (ctl.status == 0 && ctl.toofull != 0));
+			bool	heap_short = (dict->heap_usage + ctl.heap_need > dict->heap_size);
+			bool	entries_short = (keys_after > dict->entries_cap);
+
+			if (ctl.status != 0 && !nospace)
+			{
+				/* the claims of this call leave the table; the entries were never touched */
+				rc = rebuild(dict, dict->nslots);
+				return rc != 0 ? rc : ctl.status;
+			}
+			if (!nospace && !heap_short && !entries_short)
+				break;
+			if (turn >= 40 || keys_after >= ((size_t)1 << 29))
+			{
+				(void)rebuild(dict, dict->nslots);
+				return StromError_DataStoreNoSpace;
+			}
+			if (heap_short)
+			{
+				size_t	need = std::max(dict->heap_usage + (size_t)ctl.heap_need, 2 * dict->heap_size);
+				if ((rc = grow(&dict->heap, dict->heap_usage, need)) != 0)
+					return rc;
+				dict->heap_size = need;
+			}
+			if (entries_short)
+			{
+				size_t	need = std::max(keys_after, 2 * (size_t)dict->entries_cap);
+				if ((rc = grow(&dict->entries, dict->nkeys, need)) != 0)
+					return rc;
+				dict->entries_cap = (cl_uint)need;
+			}
+			/* a table that ran full has told of the keys it could hold only: eight times the slots
+			 * then, so that a dictionary begun without a hint reaches any size in a few turns */
+			cl_uint	nslots = pow2_at_least(4 * keys_after);
+			if (nospace)
+				nslots = std::max(nslots, pow2_at_least(8 * (size_t)dict->nslots));
+			nslots = std::max(nslots, dict->nslots);
+			if ((rc = rebuild(dict, nslots)) != 0)
+				return rc;
+		}
+		/* the counters move only when settle and emit have been seen to end clean: until then the
+		 * dictionary is what the entries below 'nkeys' say */
+		cl_uint		nnew = ctl.nnew, nnull = ctl.nnull;
+		cl_ulong	heap_need = ctl.heap_need;
+		rc = 0;
+		if (nnew > 0)
+		{
+			textdict_args a = base_args(dict);
+			a.newkeys = (cl_ulong)(uintptr_t)newkeys;
+			a.colidx = colidx;
+			a.nnew = nnew;
+			void	   *args[] = { &a_src, &a };
+			rc = launch(dict, K_SETTLE, grid_for(nnew), args);
+		}
+		if (rc == 0)
+		{
+			textdict_args a = base_args(dict);
+			a.nkeys = dict->nkeys + nnew;
+			a.row_slot = (cl_ulong)(uintptr_t)row_slot;
+			a.out_values = (cl_ulong)(uintptr_t)out_values;
+			a.out_notnull = (cl_ulong)(uintptr_t)out_notnull;
+			void	   *args[] = { &a_src, &a };
+			if ((rc = launch(dict, K_EMIT, grid_for(nrows), args)) == 0 && (rc = read_ctl(dict, &ctl)) == 0)
+				rc = ctl.status;				/* settle or emit met a word no launch writes */
+		}
+		if (rc != 0)
+		{
+			/* back to the keys before the call: their entries and heap bytes were not touched */
+			(void)hipStreamSynchronize(stream);
+			(void)rebuild(dict, dict->nslots);
+			return rc;
+		}
+		dict->nkeys += nnew;
+		dict->heap_usage += heap_need;
+		*p_nnull = nnull;
+		if (2 * (size_t)dict->nkeys > dict->nslots)
+			return rebuild(dict, pow2_at_least(4 * (size_t)dict->nkeys));
+		return 0;
+	}
+};
+
+void
+textdict_free(Device *dev, strom_textdict *dict)
+{
+	for (void *p : { (void *)dict->slots, (void *)dict->entries, (void *)dict->heap, (void *)dict->ctl })
+		if (p)
+			dev->pool.release(p);
+	dict->slots = nullptr;
+	dict->entries = nullptr;
+	dict->heap = nullptr;
+	dict->ctl = nullptr;
+}
+
+/* empty tables sized by the hint */
+int
+textdict_allocate(Device *dev, strom_textdict *dict)
+{
+	dict->nkeys = 0;
+	dict->heap_usage = 0;
+	dict->nslots = pow2_at_least(4 * (size_t)dict->nkeys_hint);
+	dict->entries_cap = std::max<cl_uint>(dict->nkeys_hint, 4);
+	dict->heap_size = 16 * (size_t)dict->entries_cap;
+	dict->slots = (cl_ulong *)dev->pool.alloc(sizeof(cl_ulong) * (size_t)dict->nslots);
+	dict->entries = (textdict_entry *)dev->pool.alloc(sizeof(textdict_entry) * (size_t)dict->entries_cap);
+	dict->heap = (char *)dev->pool.alloc(dict->heap_size);
+	dict->ctl = (textdict_ctl *)dev->pool.alloc(sizeof(textdict_ctl));
+	if (!dict->slots || !dict->entries || !dict->heap || !dict->ctl)
+		return StromError_OutOfMemory;
+	(void)hipSetDevice(dev->hip_id);
+	if (hipMemsetAsync(dict->slots, 0, sizeof(cl_ulong) * (size_t)dict->nslots, dev->streams[0]) != hipSuccess ||
+		hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), dev->streams[0]) != hipSuccess ||
+		hipStreamSynchronize(dev->streams[0]) != hipSuccess)
+		return StromError_HipInternal;
+	return 0;
+}
+
+}	/* namespace */
+
+extern "C" strom_textdict *
+strom_textdict_create(int type_oid, uint32_t nkeys_hint, int dindex, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = 0;
+	if ((type_oid != STROM_TEXTOID && type_oid != STROM_BPCHARNOID) || nkeys_hint > (1u << 28))
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	Device *dev = get_device(dindex);
+	if (!dev)
+	{
+		*p_errcode = StromError_ServerNotReady;
+		return nullptr;
+	}
+	strom_textdict *dict = new strom_textdict();
+	dict->type_oid = type_oid;
+	dict->dindex = dindex;
+	dict->blank_padded = (type_oid == STROM_BPCHARNOID);
+	dict->nkeys_hint = nkeys_hint;
+	if ((*p_errcode = textdict_allocate(dev, dict)) != 0)
+	{
+		textdict_free(dev, dict);
+		delete dict;
+		return nullptr;
+	}
+	return dict;
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+extern "C" uint32_t
+strom_textdict_num_keys(strom_textdict *dict)
+{
+	return dict ? dict->nkeys : 0;
+}
+
+extern "C" void
+strom_textdict_reset(strom_textdict *dict)
+{
+	Device *dev = dict ? get_device(dict->dindex) : nullptr;
+	if (!dev)
+		return;
+	(void)hipSetDevice(dev->hip_id);
+	dict->nkeys = 0;
+	dict->heap_usage = 0;
+	(void)hipMemsetAsync(dict->slots, 0, sizeof(cl_ulong) * (size_t)dict->nslots, dev->streams[0]);
+	(void)hipStreamSynchronize(dev->streams[0]);
+}
+
+extern "C" void
+strom_textdict_release(strom_textdict *dict)
+{
+	if (!dict)
+		return;
+	Device *dev = get_device(dict->dindex);
+	if (dev)
+	{
+		(void)hipSetDevice(dev->hip_id);
+		(void)hipStreamSynchronize(dev->streams[0]);
+		textdict_free(dev, dict);
+	}
+	delete dict;
+}
+
+extern "C" int
+strom_textdict_kernel_ns(strom_textdict *dict, uint64_t *ns_out)
+{
+	if (!dict || !ns_out)
+		return StromError_BadRequestMessage;
+	memcpy(ns_out, dict->kern_ns, sizeof(dict->kern_ns));
+	return 0;
+}
+
+extern "C" strom_devprog_key
+strom_textdict_program(strom_textdict *dict)
+{
+	return dict ? dict->program : 0;
+}
+
+extern "C" long
+strom_textdict_fetch(strom_textdict *dict, void *heap_out, size_t heaplen,
+					 uint64_t *offsets_out, size_t noffsets, size_t *p_heap_bytes)
+{
+	STROM_ABI_TRY
+	if (!dict)
+		return -(long)StromError_BadRequestMessage;
+	if (p_heap_bytes)
+		*p_heap_bytes = dict->heap_usage;
+	if (!heap_out)
+		return (long)dict->nkeys;
+	Device *dev = get_device(dict->dindex);
+	if (!dev)
+		return -(long)StromError_ServerNotReady;
+	if (heaplen < dict->heap_usage || noffsets < dict->nkeys || !offsets_out)
+		return -(long)StromError_DataStoreNoSpace;
+	(void)hipSetDevice(dev->hip_id);
+	std::vector<textdict_entry> entries(dict->nkeys);
+	if ((dict->heap_usage > 0 &&
+		 hipMemcpy(heap_out, dict->heap, dict->heap_usage, hipMemcpyDeviceToHost) != hipSuccess) ||
+		(dict->nkeys > 0 &&
+		 hipMemcpy(entries.data(), dict->entries, sizeof(textdict_entry) * dict->nkeys,
+				   hipMemcpyDeviceToHost) != hipSuccess))
+		return -(long)StromError_HipInternal;
+	for (cl_uint id = 0; id < dict->nkeys; id++)
+	{
+		if (entries[id].off >= dict->heap_usage)
+			return -(long)StromError_SanityCheckViolation;
+		offsets_out[id] = entries[id].off;
+	}
+	return (long)dict->nkeys;
+	STROM_ABI_CATCH(-(long)StromError_OutOfMemory, (int *)nullptr)
+}
+
+extern "C" strom_dstore *
+strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, int nkeys,
+					  strom_dstore *src, const int32_t *carry_colidx, int ncarry, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = StromError_BadRequestMessage;
+	if (!dicts || !key_colidx || nkeys < 1 || nkeys > STROM_PREAGG_MAXKEYS || !src || ncarry < 0 ||
+		ncarry > 64 || (ncarry > 0 && !carry_colidx))
+		return nullptr;
+	for (int i = 0; i < nkeys; i++)
+		if (!dicts[i] || dicts[i]->dindex != src->dindex)
+			return nullptr;
+	if (src->head.format != KDS_FORMAT_COLUMN || src->head.ncols < 1 || src->head.ncols > 1600)
+		return nullptr;
+	Device *dev = get_device(src->dindex);
+	if (!dev)
+	{
+		*p_errcode = StromError_ServerNotReady;
+		return nullptr;
+	}
+	int		src_ncols = (int)src->head.ncols;
+	cl_uint	nrows = src->head.nitems;
+	for (int i = 0; i < nkeys; i++)
+		if (key_colidx[i] < 0 || key_colidx[i] >= src_ncols)
+			return nullptr;
+	for (int i = 0; i < ncarry; i++)
+		if (carry_colidx[i] < 0 || carry_colidx[i] >= src_ncols)
+			return nullptr;
+	(void)hipSetDevice(dev->hip_id);
+	/* the source's column metadata and directory */
+	std::vector<char> shead(KDS_COLUMN_HEAD_LENGTH(src_ncols), 0);
+	if (shead.size() > src->length)
+		return nullptr;
+	if (hipMemcpy(shead.data(), src->devptr, shead.size(), hipMemcpyDeviceToHost) != hipSuccess)
+	{
+		*p_errcode = StromError_HipInternal;
+		return nullptr;
+	}
+	const kern_data_store *skds = (const kern_data_store *)shead.data();
+	const kern_coldir *scd = KERN_DATA_STORE_COLDIR(skds);
+	size_t	varwidth = sizeof(cl_ulong) * (size_t)nrows;
+	size_t	bitmap_len = sizeof(cl_uint) * (((size_t)nrows + 31) / 32);
+	for (int i = 0; i < nkeys; i++)
+	{
+		const kern_coldir *cd = &scd[key_colidx[i]];
+		if (skds->colmeta[key_colidx[i]].attlen != -1)
+			return nullptr;							/* not a varlena column */
+		if ((size_t)cd->values_off + varwidth > src->length ||
+			(cd->nulls_off != 0 && (size_t)cd->nulls_off + bitmap_len > src->length))
+		{
+			*p_errcode = StromError_DataStoreCorruption;
+			return nullptr;
+		}
+	}
+	for (int i = 0; i < ncarry; i++)
+	{
+		const kern_coldir *cd = &scd[carry_colidx[i]];
+		int		attlen = skds->colmeta[carry_colidx[i]].attlen;
+		if (!(attlen == 1 || attlen == 2 || attlen == 4 || attlen == 8))
+			return nullptr;							/* varlena columns are not carried */
+		if ((size_t)cd->values_off + (size_t)attlen * nrows > src->length ||
+			(cd->nulls_off != 0 && (size_t)cd->nulls_off + bitmap_len > src->length))
+		{
+			*p_errcode = StromError_DataStoreCorruption;
+			return nullptr;
+		}
+	}
+	*p_errcode = 0;
+	Encoder	enc;
+	enc.dev = dev;
+	enc.stream = dev->streams[0];
+	enc.timed = perfmon_enabled();
+	int		errcode = 0;
+	strom_devprog_key progkey = 0;
+	Program *prog = textdict_program(&errcode, &progkey);
+	static const char *const names[4] = { "textdict_probe", "textdict_settle", "textdict_emit", "textdict_rebuild" };
+	for (int i = 0; prog && i < 4; i++)
+		if (!(enc.fn[i] = prog->get_function(dev, names[i], &errcode)))
+			prog = nullptr;
+	if (!prog)
+	{
+		*p_errcode = errcode ? errcode : StromError_ProgramBuildFailure;
+		return nullptr;
+	}
+	enc.block = textdict_block();
+	enc.max_grid = (unsigned)dev->prop.multiProcessorCount * 8;
+	if (const char *v = getenv("STROM_TEXTDICT_MAX_GRID"))		/* tests: grid strides on small chunks */
+		if (atoi(v) > 0)
+			enc.max_grid = (unsigned)atoi(v);
+
+	/* the encoded chunk: id columns (bitmap room always laid out, named in the directory only
+	 * when the column has a NULL), then the carried columns as they are */
+	int		ncols = nkeys + ncarry;
+	std::vector<char> hbuf(KDS_COLUMN_HEAD_LENGTH(ncols), 0);
+	kern_data_store *head = (kern_data_store *)hbuf.data();
+	head->ncols = ncols;
+	kern_coldir *cd = KERN_DATA_STORE_COLDIR(head);
+	std::vector<size_t> nulls_at(ncols, 0);
+	size_t	off = hbuf.size();
+	for (int c = 0; c < ncols; c++)
+	{
+		const kern_colmeta *scm = (c < nkeys ? nullptr : &skds->colmeta[carry_colidx[c - nkeys]]);
+		int		attlen = (scm ? scm->attlen : 4);
+		head->colmeta[c].attbyval = 1;
+		head->colmeta[c].attalign = (cl_char)attlen;
+		head->colmeta[c].attlen = (cl_short)attlen;
+		head->colmeta[c].attnum = (cl_short)(c + 1);
+		head->colmeta[c].attcacheoff = -1;
+		cd[c].values_off = (cl_uint)off;
+		off += KDS_COLUMN_VALUES_LENGTH(attlen, nrows);
+		if (c < nkeys || scd[carry_colidx[c - nkeys]].nulls_off != 0)
+		{
+			nulls_at[c] = off;
+			off += KDS_COLUMN_NULLS_LENGTH(nrows);
+		}
+		if (off > 0xffffffffUL)
+		{
+			*p_errcode = StromError_DataStoreOutOfRange;
+			return nullptr;
+		}
+	}
+	head->hostptr = 0;
+	head->length = (cl_uint)off;
+	head->usage = 0;
+	head->nitems = nrows;
+	head->nrooms = nrows;
+	head->format = KDS_FORMAT_COLUMN;
+	head->tdtypeid = skds->tdtypeid;
+	head->tdtypmod = skds->tdtypmod;
+
+	char	   *d_dst = (char *)dev->pool.alloc(off);
+	cl_uint	   *d_row_slot = (cl_uint *)dev->pool.alloc(sizeof(cl_uint) * std::max<size_t>(nrows, 1));
+	textdict_newkey *d_newkeys = (textdict_newkey *)dev->pool.alloc(sizeof(textdict_newkey) * std::max<size_t>(nrows, 1));
+	strom_dstore *result = nullptr;
+	do {
+		if (!d_dst || !d_row_slot || !d_newkeys)
+		{
+			*p_errcode = StromError_OutOfMemory;
+			break;
+		}
+		std::vector<cl_uint> nnull(nkeys, 0);
+		for (int i = 0; i < nkeys && *p_errcode == 0; i++)
+		{
+			memset(dicts[i]->kern_ns, 0, sizeof(dicts[i]->kern_ns));
+			dicts[i]->program = progkey;
+			*p_errcode = enc.encode_column(dicts[i], src, (cl_uint)key_colidx[i], d_row_slot, d_newkeys,
+										   d_dst + cd[i].values_off, d_dst + nulls_at[i], &nnull[i]);
+		}
+		if (*p_errcode != 0)
+			break;
+		for (int c = 0; c < ncols; c++)
+		{
+			if (c < nkeys)
+			{
+				/* the ids' domain: what a dense session of GpuPreAgg is opened with */
+				cl_uint		nk = dicts[c]->nkeys;
+				cd[c].nulls_off = (nnull[c] > 0 ? (cl_uint)nulls_at[c] : 0);
+				cd[c].stat_flags = (nk > 0 && nnull[c] < nrows ? KDS_COLSTAT_MINMAX : 0);
+				cd[c].minval = 0;
+				cd[c].maxval = (nk > 0 ? (cl_long)nk - 1 : 0);
+				continue;
+			}
+			const kern_coldir *from = &scd[carry_colidx[c - nkeys]];
+			size_t		width = (size_t)head->colmeta[c].attlen * nrows;
+			cd[c].nulls_off = (cl_uint)nulls_at[c];
+			cd[c].stat_flags = from->stat_flags;
+			cd[c].minval = from->minval;
+			cd[c].maxval = from->maxval;
+			if ((width > 0 &&
+				 hipMemcpyAsync(d_dst + cd[c].values_off, (const char *)src->devptr + from->values_off, width,
+								hipMemcpyDeviceToDevice, enc.stream) != hipSuccess) ||
+				(nulls_at[c] != 0 && bitmap_len > 0 &&
+				 hipMemcpyAsync(d_dst + nulls_at[c], (const char *)src->devptr + from->nulls_off, bitmap_len,
+								hipMemcpyDeviceToDevice, enc.stream) != hipSuccess))
+			{
+				*p_errcode = StromError_HipInternal;
+				break;
+			}
+		}
+		if (*p_errcode != 0)
+			break;
+		if (hipMemcpyAsync(d_dst, hbuf.data(), hbuf.size(), hipMemcpyHostToDevice, enc.stream) != hipSuccess ||
+			hipStreamSynchronize(enc.stream) != hipSuccess)
+		{
+			*p_errcode = StromError_HipInternal;
+			break;
+		}
+		result = new strom_dstore{d_dst, off, src->dindex, true, {}};
+		memcpy(&result->head, head, offsetof(kern_data_store, colmeta));
+	} while (0);
+	if (!result)
+		(void)hipStreamSynchronize(enc.stream);
+	if (d_row_slot) dev->pool.release(d_row_slot);
+	if (d_newkeys) dev->pool.release(d_newkeys);
+	if (!result && d_dst) dev->pool.release(d_dst);
+	return result;
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}

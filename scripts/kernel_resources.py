@@ -2,6 +2,7 @@
 kernel's register / LDS / scratch use from the code object's metadata.
 
 usage: python scripts/kernel_resources.py gpupreagg "(gpupreagg ...)"
+       python scripts/kernel_resources.py textdict -      (fixed programs: ingest, textdict)
 """
 import re
 import subprocess
@@ -30,6 +31,13 @@ def main():
                       '#include "strom_numeric.h"\n#include "strom_ingest.h"\n')
             extra_flags = 0
         cg = _S()
+    elif kind == "textdict":
+        from pg_strom_amd import textdict
+
+        class _S(object):
+            source = textdict.program_source()
+            extra_flags = 0
+        cg = _S()
     elif kind == "gpuscan":
         cg = runtime.codegen_gpuscan(spec)
     elif kind == "gpupreagg":
@@ -42,13 +50,15 @@ def main():
     path = os.path.join(os.path.dirname(runtime.__file__), "_cache", "%016x.hsaco" % prog.key)
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", path],
                          capture_output=True, text=True).stdout
-    for m in re.finditer(r"\.name:\s+(\S+)(.*?)\.wavefront_size", out, re.S):
-        body = m.group(2)
+    # a kernel's metadata map is sorted by key: .agpr_count first, .wavefront_size last
+    for m in re.finditer(r"\.agpr_count:.*?\.wavefront_size", out, re.S):
+        body = m.group(0)
+        name = re.search(r"\.name:\s+(\S+)", body).group(1)
         get = lambda k: re.search(r"\.%s:\s+(\d+)" % k, body)
         vals = {k: (get(k).group(1) if get(k) else "?")
                 for k in ("vgpr_count", "agpr_count", "sgpr_count",
                           "group_segment_fixed_size", "private_segment_fixed_size")}
-        print(m.group(1), vals)
+        print(name, vals)
 
 
 if __name__ == "__main__":

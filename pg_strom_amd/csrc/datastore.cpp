@@ -356,30 +356,34 @@ column_layout(int ncols, const strom_column_input *cols, uint32_t nrooms,
 	return off;
 }
 
-/* a 64-bit numeric image's value rounded away from zero to an integer (KDS_COLSTAT_INTPART);
- * false when that does not fit int64 */
+/* floor and ceil of a 64-bit numeric image's value (KDS_COLSTAT_INTPART); false when its
+ * integer part does not fit int64 */
 bool
-numeric_image_outward(uint64_t image, int64_t *p_out)
+numeric_image_floor_ceil(uint64_t image, int64_t *p_floor, int64_t *p_ceil)
 {
 	int			expo = (int)((int64_t)image >> 58);
 	bool		sign = ((image >> 57) & 1) != 0;
 	unsigned __int128 m = image & ((1ULL << 57) - 1);
+	unsigned __int128 up;			/* the magnitude rounded up; 'm' becomes it rounded down */
 
 	if (expo >= 0)
 	{
 		for (int i = 0; i < expo && m < ((unsigned __int128)1 << 64); i++)
 			m *= 10;
+		up = m;
 	}
 	else
 	{
 		unsigned __int128 d = 1;
 		for (int i = 0; i < -expo && d < ((unsigned __int128)1 << 64); i++)
 			d *= 10;
-		m = (m + d - 1) / d;
+		up = (m + d - 1) / d;
+		m = m / d;
 	}
-	if (m > (unsigned __int128)INT64_MAX)
+	if (up > (unsigned __int128)INT64_MAX)
 		return false;
-	*p_out = (sign ? -(int64_t)m : (int64_t)m);
+	*p_floor = (sign ? -(int64_t)up : (int64_t)m);
+	*p_ceil = (sign ? -(int64_t)m : (int64_t)up);
 	return true;
 }
 
@@ -394,7 +398,7 @@ column_minmax(const strom_column_input &c, uint32_t nrows, kern_coldir *cd)
 		return;				/* type unknown (converted chunk): no zone map */
 	if (c.type_oid == STROM_NUMERICOID)
 	{
-		/* 64-bit images: bounds of the values' integer parts, outward (strom_kds.h) */
+		/* 64-bit images: floor(min) and ceil(max) of the values (strom_kds.h) */
 		int64_t	lo = 0, hi = 0;
 		if (c.attlen != 8)
 			return;
@@ -403,12 +407,12 @@ column_minmax(const strom_column_input &c, uint32_t nrows, kern_coldir *cd)
 			if (is_null(c, r))
 				continue;
 			uint64_t	image;
-			int64_t		v;
+			int64_t		vlo, vhi;
 			memcpy(&image, (const char *)c.values + 8 * (size_t)r, 8);
-			if (!numeric_image_outward(image, &v))
+			if (!numeric_image_floor_ceil(image, &vlo, &vhi))
 				return;			/* a value beyond int64: no bound to give */
-			if (!any || v < lo) lo = v;
-			if (!any || v > hi) hi = v;
+			if (!any || vlo < lo) lo = vlo;
+			if (!any || vhi > hi) hi = vhi;
 			any = true;
 		}
 		if (any)

@@ -311,7 +311,7 @@ ingest_minmax(kern_data_store *dst, const cl_int *type_oids)
 	if (oid == STROM_NUMERICOID)
 	{
 		/*
-		 * 64-bit numeric images: the bounds are of the VALUES' integer parts, rounded outward
+		 * 64-bit numeric images: the bounds are floor(min) and ceil(max) of the VALUES
 		 * (KDS_COLSTAT_INTPART, strom_kds.h) -- the images' own bit patterns do not order like the
 		 * values.  A value beyond int64 spoils the column's bounds (the full range: dropped by
 		 * ingest_finish).
@@ -327,6 +327,7 @@ ingest_minmax(kern_data_store *dst, const cl_int *type_oids)
 			bool		sign = ((image >> 57) & 1) != 0;
 			cl_ulong	m = image & ((1UL << 57) - 1);
 			bool		fits = true;
+			cl_ulong	up;				/* the magnitude rounded up; 'm' becomes it rounded down */
 			if (expo >= 0)
 			{
 				for (cl_int i = 0; i < expo && fits; i++)
@@ -334,6 +335,7 @@ ingest_minmax(kern_data_store *dst, const cl_int *type_oids)
 					fits = (m <= 0x7fffffffffffffffUL / 10);
 					m *= 10;
 				}
+				up = m;
 			}
 			else
 			{
@@ -341,17 +343,21 @@ ingest_minmax(kern_data_store *dst, const cl_int *type_oids)
 				cl_int		i = 0;
 				for (; i < -expo && d <= 0xffffffffffffffffUL / 10; i++)
 					d *= 10;
-				m = (i < -expo ? (m != 0 ? 1UL : 0UL) : (m / d + (m % d != 0 ? 1UL : 0UL)));
+				/* (a divisor beyond 64 bits is beyond every 57-bit mantissa) */
+				up = (i < -expo ? (m != 0 ? 1UL : 0UL) : (m / d + (m % d != 0 ? 1UL : 0UL)));
+				m = (i < -expo ? 0UL : m / d);
 			}
-			if (!fits || m > 0x7fffffffffffffffUL)
+			if (!fits || up > 0x7fffffffffffffffUL)
 			{
 				mn = 0UL;
 				mx = ~0UL;
 				continue;
 			}
-			cl_ulong	key = (cl_ulong)(sign ? -(cl_long)m : (cl_long)m) ^ 0x8000000000000000UL;
-			mn = (key < mn ? key : mn);
-			mx = (key > mx ? key : mx);
+			/* floor for the minimum, ceil for the maximum */
+			cl_ulong	klo = (cl_ulong)(sign ? -(cl_long)up : (cl_long)m) ^ 0x8000000000000000UL;
+			cl_ulong	khi = (cl_ulong)(sign ? -(cl_long)m : (cl_long)up) ^ 0x8000000000000000UL;
+			mn = (klo < mn ? klo : mn);
+			mx = (khi > mx ? khi : mx);
 		}
 	}
 	else

@@ -1339,7 +1339,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 			 hipModuleLaunchKernel(fn_proj, pgrid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) != hipSuccess ||
 			 (timing && hipEventRecord(ev[3], stream) != hipSuccess) ||
 			 (any_zone_map &&
-			  hipModuleLaunchKernel(fn_mm, std::min(grid, (unsigned)dev->prop.multiProcessorCount),
+			  hipModuleLaunchKernel(fn_mm, ingest_grid_cap(std::min(grid, (unsigned)dev->prop.multiProcessorCount)),
 									(unsigned)ncols, 1, 256, 1, 1, 0, stream, args_mm, nullptr) != hipSuccess)))
 		{
 			*p_errcode = StromError_HipInternal;

@@ -204,6 +204,7 @@ strom_dstore_to_column(strom_dstore *src, const int32_t *type_oids, int ntypes,
 		void	   *args_fin[] = { &a_dst, &a_oids, &a_flags };
 		unsigned	nwg = (unsigned)std::min<size_t>(((size_t)nitems + 255) / 256,
 													 (size_t)dev->prop.multiProcessorCount * 8);
+		nwg = ingest_grid_cap(nwg);
 		(void)hipEventRecord(ev0, stream);
 		if (nwg > 0 &&
 			hipModuleLaunchKernel(fn_main, nwg, 1, 1, 256, 1, 1, 0, stream, args_main, nullptr) != hipSuccess)
@@ -215,6 +216,7 @@ strom_dstore_to_column(strom_dstore *src, const int32_t *type_oids, int ntypes,
 		void	   *args_mm[] = { &a_dst, &a_oids };
 		unsigned	mmgrid = (unsigned)std::min<size_t>(((size_t)nitems + 255) / 256,
 														(size_t)dev->prop.multiProcessorCount);	/* one work-group per CU and column: see ingest_minmax */
+		mmgrid = ingest_grid_cap(mmgrid);
 		if (type_oids && mmgrid > 0 &&
 			hipModuleLaunchKernel(fn_mm, mmgrid, (unsigned)ncols, 1, 256, 1, 1, 0, stream,
 								  args_mm, nullptr) != hipSuccess)

@@ -18,6 +18,7 @@ extern "C" hipError_t hipExtModuleLaunchKernel(hipFunction_t f, uint32_t globalW
 											   hipEvent_t startEvent, hipEvent_t stopEvent, uint32_t flags);
 #include <atomic>
 #include <condition_variable>
+#include <cstdlib>
 #include <deque>
 #include <functional>
 #include <map>
@@ -303,6 +304,17 @@ program_accepts_format(const Program *prog, cl_int format)
 {
 	return !(prog->extra_flags & DEVTYPE_IS_VARLENA) ||
 		format == KDS_FORMAT_ROW || format == KDS_FORMAT_ROW_FLAT || format == KDS_FORMAT_COLUMN;
+}
+/* STROM_INGEST_MAX_GRID (host policy, read on every call; tests: grid strides on small chunks):
+ * caps the work-groups of the ingest_to_column* kernels and of the ingest_minmax launch
+ * (ingest.cpp, and the join's COLUMN projection in gpuhashjoin.cpp) */
+inline unsigned
+ingest_grid_cap(unsigned grid)
+{
+	if (const char *v = getenv("STROM_INGEST_MAX_GRID"))
+		if (atoi(v) > 0 && (unsigned)atoi(v) < grid)
+			return (unsigned)atoi(v);
+	return grid;
 }
 bool		perfmon_enabled();
 strom_task_impl *task_create(Device *dev, strom_done_cb done, void *arg);

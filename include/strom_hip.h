@@ -610,6 +610,51 @@ void		strom_textdict_reset(strom_textdict *dict);
 void		strom_textdict_release(strom_textdict *dict);
 
 /* ------------------------------------------------------------------ *
+ * GROUP BY text across sessions and GPUs: one numbering for several dictionaries
+ *
+ * Sessions of several shards (row ranges of one table, one process per GPU) can be merged --
+ * strom_gpupreagg_merge, _exchange_local, _allreduce, _reduce_scatter -- only if they call the same
+ * key by the same id.  Every shard encodes under a dictionary of its own; then every shard builds
+ * the same UNION dictionary by absorbing the shards' key images (what strom_textdict_fetch hands
+ * out: heap bytes + offsets[id]) in rank order, and rewrites the id columns of its encoded chunks
+ * through the id map its own image got.  The numbering is a function of the images and their
+ * order alone -- Python's  for k in image: ids.setdefault(k, len(ids))  with 'ids' starting as the
+ * keys the dictionary holds: a key it holds keeps its id, the others get num_keys, num_keys+1, ...
+ * in order of first appearance in the image, equal keys of one image (character(n): 'a', 'a ')
+ * get one id -- so the union dictionaries of all ranks are identical without further talk, and
+ * the sessions share the dense domain {0, num_keys} of the union.
+ *
+ * One absorb / recode at a time per dictionary and chunk: the caller serialises, as with an
+ * encode.  A map remembers the dictionary it was made by and must be released before it.
+ * Refused with StromError_BadRequestMessage before any launch: a NULL handle, dst == src,
+ * dictionaries of different type or device, nkeys > 0 with a NULL heap or NULL offsets, a recode
+ * target that is not a resident COLUMN chunk, a recode column that is not by-value with attlen 4
+ * (or named twice), ncols outside 1..STROM_PREAGG_MAXKEYS, a map of another device than the chunk's.
+ * ------------------------------------------------------------------ */
+typedef struct strom_keymap strom_keymap;		/* device-resident int4[n]: id in the image -> id under dst */
+/* dst absorbs a host image of nkeys complete varlena datums; blocks like an encode.  The image is
+ * checked on the host first (every offset inside the heap, every datum inside it by its own
+ * length, no external or compressed header): StromError_DataStoreCorruption, no kernel runs.  An
+ * absorb that ends in an error leaves dst as it was: the same keys under the same ids. */
+strom_keymap *strom_keyunion_absorb(strom_textdict *dst, const void *heap, size_t heaplen,
+									const uint64_t *offsets, uint32_t nkeys, int *p_errcode);
+/* ... the keys of src in id order, read where they lie on the device (no host copy); src is unchanged */
+strom_keymap *strom_keyunion_absorb_dict(strom_textdict *dst, strom_textdict *src, int *p_errcode);
+uint32_t	strom_keymap_size(strom_keymap *map);
+int			strom_keymap_fetch(strom_keymap *map, int32_t *out, size_t n);
+void		strom_keymap_release(strom_keymap *map);
+/* ids[row] = maps[i][ids[row]] over the int4 column colidx[i] of an encoded chunk, in place.  A NULL
+ * row's id becomes 0 without a lookup; an id >= the map's size on a non-NULL row:
+ * StromError_DataStoreCorruption.  The column's zone map becomes {0, num_keys-1} of the map's
+ * dictionary as it is at the time of the call; notnull bitmaps and the other columns are not
+ * touched.  After an error the id columns named in the call are unspecified: release the chunk. */
+int			strom_keyunion_recode(strom_dstore *encoded, const int32_t *colidx,
+								  strom_keymap *const *maps, int ncols);
+/* device time, when strom_set_perfmon(1): ns_out[6] = the last absorb into dst (probe, ranks, settle,
+ * emit, rebuild) and the last recode through a map of dst (measurement) */
+int			strom_keyunion_kernel_ns(strom_textdict *dst, uint64_t *ns_out);
+
+/* ------------------------------------------------------------------ *
  * multi-GPU: merge of the per-GPU GpuPreAgg tables over RCCL (xGMI)
  *
  * The reference has no collective (SURVEY.md section 2.3 / section 5

@@ -197,6 +197,14 @@ PROTOTYPES = {
     "strom_textdict_program": (c_uint64, [c_void_p]),
     "strom_textdict_reset": (None, [c_void_p]),
     "strom_textdict_release": (None, [c_void_p]),
+    "strom_keyunion_absorb": (c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint32,
+                                         ctypes.POINTER(c_int)]),
+    "strom_keyunion_absorb_dict": (c_void_p, [c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "strom_keymap_size": (c_uint32, [c_void_p]),
+    "strom_keymap_fetch": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "strom_keymap_release": (None, [c_void_p]),
+    "strom_keyunion_recode": (c_int, [c_void_p, ctypes.POINTER(c_int32), ctypes.POINTER(c_void_p), c_int]),
+    "strom_keyunion_kernel_ns": (c_int, [c_void_p, ctypes.POINTER(c_uint64)]),
     "strom_task_wait": (c_int, [c_void_p, ctypes.POINTER(strom_perfmon)]),
     "strom_task_release": (None, [c_void_p]),
     "strom_task_devptr": (c_void_p, [c_void_p]),

@@ -420,4 +420,50 @@ static_assert(sizeof(textdict_entry) == 16, "textdict_entry");
 static_assert(sizeof(textdict_newkey) == 8, "textdict_newkey");
 static_assert(sizeof(textdict_args) == 104, "textdict_args");
 
+/* ---------------------------------------------------------------------- *
+ * union of key dictionaries (strom_textdict.h: keyunion_*, textdict.cpp)
+ * ---------------------------------------------------------------------- */
+/* one absorb: the keys of an image -- complete varlena datums in img_heap, key i at the offset read
+ * from img_offsets + i * img_stride -- enter the dictionary {slots, entries, heap}; the image is
+ * read-only for the whole absorb.  The call's status and claim count go through the dictionary's
+ * textdict_ctl (status, nnew, toofull; the other words are not used). */
+struct keyunion_args {
+	cl_ulong	slots;				/* the absorbing dictionary's, as in textdict_args */
+	cl_ulong	entries;
+	cl_ulong	heap;
+	cl_ulong	ctl;
+	cl_ulong	img_heap;			/* const char[img_heaplen] */
+	cl_ulong	img_offsets;		/* the first of nimg cl_ulong offsets into img_heap, img_stride bytes apart:
+									 * 8 = an offsets array, 16 = the 'off' words of a dictionary's entries[] */
+	cl_ulong	img_heaplen;
+	cl_ulong	key_slot;			/* cl_uint[nimg]: the slot of image key i, ~0 = failed key */
+	cl_ulong	tiles;				/* keyunion_tile[ntiles + 1], a tile being TEXTDICT_BLOCK image keys in a row:
+									 * count: its new keys; offsets: the new keys before it, [ntiles] = all */
+	cl_ulong	map;				/* emit: cl_int[nimg], id of image key i under the dictionary */
+	cl_ulong	heap_usage;			/* bytes of the heap in use before this call */
+	cl_ulong	heap_size;
+	cl_uint		img_stride;
+	cl_uint		nimg;
+	cl_uint		ntiles;
+	cl_uint		nslots;				/* power of two */
+	cl_uint		nkeys;				/* keys before this call; emit: after it */
+	cl_uint		blank_padded;
+};
+/* new keys of a tile (or before it), and the heap bytes of their datums, each rounded up to 4 */
+struct keyunion_tile {
+	cl_ulong	bytes;
+	cl_uint		count;
+	cl_uint		__pad;
+};
+/* recode: ids[row] = map[ids[row]] over the int4 column 'colidx' of a COLUMN chunk */
+struct keyunion_recode_args {
+	cl_ulong	map;				/* const cl_int[mapsize] */
+	cl_ulong	status;				/* cl_int: worst row error */
+	cl_uint		mapsize;
+	cl_uint		colidx;
+};
+static_assert(sizeof(keyunion_args) == 120, "keyunion_args");
+static_assert(sizeof(keyunion_tile) == 16, "keyunion_tile");
+static_assert(sizeof(keyunion_recode_args) == 24, "keyunion_recode_args");
+
 #endif	/* STROM_CTL_H */

@@ -36,6 +36,10 @@
  *   textdict_emit     one row per lane: the slot's id into the int4 column of the encoded chunk
  *   textdict_rebuild  one key per lane: entries -> a cleared slot array (growth, and the way back
  *                     from a failed probe: the entries are what a probe never touches)
+ *
+ * The second half of the file (keyunion_*) lets a dictionary absorb the keys of other dictionaries
+ * with ids that do not depend on timing, and rewrites encoded id columns through the id maps that
+ * come of it: what sessions of several shards need before their tables can be merged.
  */
 #ifndef STROM_TEXTDICT_DEVICE_H
 #define STROM_TEXTDICT_DEVICE_H
@@ -476,6 +480,415 @@ textdict_rebuild(textdict_args a)
 		}
 	}
 	textdict_writeback_status(&ctl->status, errcode);
+}
+
+/* ================================================================ *
+ * union of dictionaries: the keys of an IMAGE (heap bytes + offsets, what strom_textdict_fetch
+ * hands out, or another dictionary's heap and entries) enter this dictionary, and every image
+ * key learns its id here.  New keys are numbered in IMAGE ORDER -- key i of the image, if the
+ * dictionary does not hold it and no j < i of the image equals it, becomes id K + (number of
+ * such keys before i) -- so that dictionaries that absorb the same images in the same order are
+ * identical, whatever the timing of their lanes.
+ *
+ *   keyunion_probe    one image key per lane: find or claim its slot.  The walk of textdict_probe
+ *                     written out a second time (one templated definition for both cost
+ *                     textdict_probe two VGPRs and this kernel four: DESIGN 3.8); a PENDING
+ *                     word names an index of the image.  A lane that finds its key
+ *                     under a PENDING word with a higher index lowers the word to its own index
+ *                     (one 64-bit atomic min: tag and flag bits are equal, the index decides), so
+ *                     after the launch a claimed slot names the LOWEST index of its key.  A lane
+ *                     records its slot only; nothing depends on who claimed.
+ *   keyunion_count    key i is new iff its slot holds PENDING | i; per tile of TEXTDICT_BLOCK
+ *                     image keys: how many, and the heap bytes of their datums
+ *   keyunion_offsets  one work-group: exclusive sums over the tiles, the totals behind the last
+ *   keyunion_settle   the new key of rank r (tile offset + rank inside the tile): id K + r, heap
+ *                     bytes, entry, PENDING -> tag | id, as textdict_settle does
+ *   keyunion_emit     map[i] = the id in key i's slot
+ *   keyunion_recode   ids[row] = map[ids[row]] over an id column of an encoded chunk, in place
+ *
+ * No lane waits for another here either: the ranks are three launches (count, offsets, settle),
+ * not a look-back scan; inside a tile the sums go through LDS between two work-group barriers,
+ * which every lane of the work-group reaches (tiles are handed out per work-group).
+ * ================================================================ */
+
+/* key i of the image, checked against the image the way textdict_row_datum checks a row against
+ * its chunk; a header the device does not read in place has no business in a key image */
+STROM_DEVICE cl_ulong
+keyunion_image_offset(const keyunion_args &a, cl_uint i)
+{
+	return *(const cl_ulong *)((const char *)a.img_offsets + (size_t)i * a.img_stride);
+}
+
+STROM_DEVICE cl_ulong
+keyunion_image_datum(cl_int *errcode, const keyunion_args &a, cl_uint i)
+{
+	cl_ulong	off = keyunion_image_offset(a, i);
+	cl_ulong	length = a.img_heaplen;
+
+	if (off >= length)
+	{
+		STROM_SET_ERROR(errcode, StromError_DataStoreCorruption);
+		return 0;
+	}
+	const char *addr = (const char *)a.img_heap + off;
+	cl_uchar	b0 = ((const cl_uchar *)addr)[0];
+	if (b0 == 0x01 || (b0 & 0x03) == 0x02 || off + ((b0 & 0x01) ? 1 : 4) > length)
+	{
+		STROM_SET_ERROR(errcode, StromError_DataStoreCorruption);
+		return 0;
+	}
+	cl_uint		size = strom_varsize_any(addr);
+	if (off + size > length || size < ((b0 & 0x01) ? 1u : 4u))
+	{
+		STROM_SET_ERROR(errcode, StromError_DataStoreCorruption);
+		return 0;
+	}
+	return (cl_ulong)addr;
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_probe(keyunion_args a)
+{
+	cl_ulong   *slots = (cl_ulong *)a.slots;
+	const textdict_entry *entries = (const textdict_entry *)a.entries;
+	const char *heap = (const char *)a.heap;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	cl_uint	   *key_slot = (cl_uint *)a.key_slot;
+	const cl_uint nimg = a.nimg;
+	const cl_uint mask = a.nslots - 1;
+	const bool	blank_padded = (a.blank_padded != 0);
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < nimg; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		i = base + threadIdx.x;
+		cl_uint		myslot = TEXTDICT_NO_SLOT;
+		bool		won = false;
+		cl_int		rowerr = StromError_Success;
+		cl_ulong	datum = (i < nimg ? keyunion_image_datum(&rowerr, a, i) : 0);
+
+		if (datum != 0)
+		{
+			cl_int		len;
+			const cl_uchar *key = textdict_key_bytes(datum, blank_padded, &len);
+			cl_ulong	h = textdict_hash(datum, blank_padded);
+			cl_ulong	tag = textdict_tag(h);
+			cl_ulong	mine = tag | TEXTDICT_PENDING | i;
+			cl_uint		s = (cl_uint)h & mask;
+			bool		placed = false;
+
+			for (cl_uint step = 0; step < a.nslots; step++, s = (s + 1) & mask)
+			{
+				cl_ulong	w = textdict_load_slot(slots, s);
+
+				/* a look, not a wait (see textdict_probe) */
+				if ((step & 63) == 16 &&
+					__hip_atomic_load(&ctl->toofull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+					break;
+				if (w == 0)
+				{
+					if (__hip_atomic_compare_exchange_strong((textdict_slot_p)(slots + s), &w, mine,
+															 __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+															 __HIP_MEMORY_SCOPE_AGENT))
+					{
+						won = placed = true;
+						break;
+					}
+					/* lost: 'w' is the winner's word, looked at like any occupied slot */
+				}
+				if ((w & (TEXTDICT_OCCUPIED | TEXTDICT_TAG_MASK)) != tag)
+					continue;
+				cl_ulong	other = 0;
+				if (w & TEXTDICT_PENDING)
+				{
+					/* a key of this image, checked by the lane that claimed the slot (or lowered its word) */
+					if ((cl_uint)w < nimg)
+						other = (cl_ulong)((const char *)a.img_heap + keyunion_image_offset(a, (cl_uint)w));
+				}
+				else if ((cl_uint)w < a.nkeys)
+					other = (cl_ulong)(heap + entries[(cl_uint)w].off);
+				if (other == 0)
+				{
+					rowerr = StromError_SanityCheckViolation;	/* a word no launch writes */
+					break;
+				}
+				cl_int		olen;
+				const cl_uchar *okey = textdict_key_bytes(other, blank_padded, &olen);
+				if (strom_bytes_equal(key, len, okey, olen))
+				{
+					/* my key, claimed under a later index: the word differs from mine in the index
+					 * alone, the smaller one stays whoever comes last */
+					if ((w & TEXTDICT_PENDING) != 0 && (cl_uint)w > i)
+						(void)__hip_atomic_fetch_min((textdict_slot_p)(slots + s), mine,
+													 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					placed = true;
+					break;
+				}
+			}
+			if (placed)
+				myslot = s;
+			else if (rowerr == StromError_Success)
+				rowerr = StromError_DataStoreNoSpace;
+		}
+		if (i < nimg)
+			key_slot[i] = myslot;
+		/* a claim is a new key, whichever index ends up in its word: count them for the host's
+		 * growth decisions, and say at once when the table is lost (see textdict_probe) */
+		strom_lanemask_t winners = __ballot(won);
+		if (winners != 0)
+		{
+			int			leader = __ffsll((long long)winners) - 1;
+
+			if ((int)strom_lane_id() == leader)
+			{
+				cl_uint		k0 = atomicAdd(&ctl->nnew, (cl_uint)__popcll(winners));
+				if (2 * ((cl_ulong)a.nkeys + k0 + (cl_uint)__popcll(winners)) > (cl_ulong)a.nslots)
+					__hip_atomic_store(&ctl->toofull, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+		}
+		STROM_SET_ERROR(&errcode, rowerr);
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+/* is image key i new, and how much heap does its datum take?  (slots as the probe left them) */
+STROM_DEVICE bool
+keyunion_is_new(cl_int *errcode, const keyunion_args &a, cl_uint i, cl_uint *p_slot, cl_uint *p_size)
+{
+	cl_uint		s = ((const cl_uint *)a.key_slot)[i];
+
+	if (s >= a.nslots)
+	{
+		*errcode = StromError_SanityCheckViolation;		/* a failed key ends the absorb before this launch */
+		return false;
+	}
+	cl_ulong	w = textdict_load_slot((const cl_ulong *)a.slots, s);
+	if ((w & TEXTDICT_PENDING) == 0 || (cl_uint)w != i)
+		return false;
+	*p_slot = s;
+	*p_size = strom_varsize_any((const char *)a.img_heap + keyunion_image_offset(a, i));	/* checked by the probe */
+	return true;
+}
+
+/*
+ * exclusive sums of (count, bytes) over the lanes of a work-group in thread order, and the totals.
+ * Every lane of the work-group calls it.
+ */
+STROM_DEVICE void
+keyunion_block_sums(cl_uint count, cl_ulong bytes, cl_uint *p_count_before, cl_ulong *p_bytes_before,
+					cl_uint *p_count_total, cl_ulong *p_bytes_total)
+{
+	__shared__ cl_uint	wave_count[TEXTDICT_BLOCK / STROM_WAVE];
+	__shared__ cl_ulong	wave_bytes[TEXTDICT_BLOCK / STROM_WAVE];
+	cl_uint		lane = strom_lane_id();
+	cl_uint		wave = threadIdx.x / STROM_WAVE;
+	cl_uint		csum = count;
+	cl_ulong	bsum = bytes;
+
+#pragma unroll
+	for (int d = 1; d < STROM_WAVE; d <<= 1)
+	{
+		cl_uint		oc = __shfl_up(csum, d, STROM_WAVE);
+		cl_ulong	ob = (cl_ulong)__shfl_up((unsigned long long)bsum, d, STROM_WAVE);
+		if (lane >= (cl_uint)d)
+		{
+			csum += oc;
+			bsum += ob;
+		}
+	}
+	if (lane == STROM_WAVE - 1)
+	{
+		wave_count[wave] = csum;
+		wave_bytes[wave] = bsum;
+	}
+	__syncthreads();
+	cl_uint		cbefore = csum - count, ctotal = 0;
+	cl_ulong	bbefore = bsum - bytes, btotal = 0;
+	for (cl_uint w = 0; w < blockDim.x / STROM_WAVE; w++)
+	{
+		if (w < wave)
+		{
+			cbefore += wave_count[w];
+			bbefore += wave_bytes[w];
+		}
+		ctotal += wave_count[w];
+		btotal += wave_bytes[w];
+	}
+	__syncthreads();							/* the arrays are free for the next call */
+	*p_count_before = cbefore;
+	*p_bytes_before = bbefore;
+	*p_count_total = ctotal;
+	*p_bytes_total = btotal;
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_count(keyunion_args a)
+{
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	keyunion_tile *tiles = (keyunion_tile *)a.tiles;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint t = blockIdx.x; t < a.ntiles; t += gridDim.x)
+	{
+		cl_uint		i = t * blockDim.x + threadIdx.x;
+		cl_uint		slot = 0, size = 0, rank, count;
+		cl_ulong	before, bytes;
+		bool		isnew = (i < a.nimg && keyunion_is_new(&errcode, a, i, &slot, &size));
+
+		keyunion_block_sums(isnew ? 1u : 0u, (cl_ulong)STROM_INTALIGN(size), &rank, &before, &count, &bytes);
+		if (threadIdx.x == 0)
+		{
+			tiles[t].bytes = bytes;
+			tiles[t].count = count;
+			tiles[t].__pad = 0;
+		}
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+/* one work-group (the host launches no more): tiles[] of counts -> tiles[] of offsets, strip by
+ * strip with the sums so far carried along; tiles[ntiles] = the totals */
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_offsets(keyunion_args a)
+{
+	keyunion_tile *tiles = (keyunion_tile *)a.tiles;
+	cl_uint		carry_count = 0;
+	cl_ulong	carry_bytes = 0;
+
+	if (blockIdx.x != 0)
+		return;
+	for (cl_uint base = 0; base < a.ntiles; base += blockDim.x)
+	{
+		cl_uint		t = base + threadIdx.x;
+		cl_uint		count = (t < a.ntiles ? tiles[t].count : 0u), cbefore, ctotal;
+		cl_ulong	bytes = (t < a.ntiles ? tiles[t].bytes : 0UL), bbefore, btotal;
+
+		keyunion_block_sums(count, bytes, &cbefore, &bbefore, &ctotal, &btotal);
+		if (t < a.ntiles)
+		{
+			tiles[t].count = carry_count + cbefore;
+			tiles[t].bytes = carry_bytes + bbefore;
+		}
+		carry_count += ctotal;
+		carry_bytes += btotal;
+	}
+	if (threadIdx.x == 0)
+	{
+		tiles[a.ntiles].count = carry_count;
+		tiles[a.ntiles].bytes = carry_bytes;
+		tiles[a.ntiles].__pad = 0;
+	}
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_settle(keyunion_args a)
+{
+	cl_ulong   *slots = (cl_ulong *)a.slots;
+	textdict_entry *entries = (textdict_entry *)a.entries;
+	char	   *heap = (char *)a.heap;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	const keyunion_tile *tiles = (const keyunion_tile *)a.tiles;
+	const cl_uint nnew = tiles[a.ntiles].count;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint t = blockIdx.x; t < a.ntiles; t += gridDim.x)
+	{
+		cl_uint		i = t * blockDim.x + threadIdx.x;
+		cl_uint		slot = 0, size = 0, rank, count;
+		cl_ulong	before, bytes;
+		bool		isnew = (i < a.nimg && keyunion_is_new(&errcode, a, i, &slot, &size));
+		cl_uint		asize = (cl_uint)STROM_INTALIGN(size);
+
+		keyunion_block_sums(isnew ? 1u : 0u, (cl_ulong)asize, &rank, &before, &count, &bytes);
+		if (!isnew)
+			continue;
+		cl_uint		r = tiles[t].count + rank;
+		cl_ulong	at = a.heap_usage + tiles[t].bytes + before;
+		if (r >= nnew || at + asize > a.heap_size)
+		{
+			errcode = StromError_SanityCheckViolation;		/* the host sized entries and heap by the totals */
+			continue;
+		}
+		const char *from = (const char *)a.img_heap + keyunion_image_offset(a, i);
+		char	   *to = heap + at;
+		cl_uint		n = 0;
+		for (; n + 8 <= size; n += 8)
+			((__attribute__((address_space(1))) textdict_unaligned_u64 *)(to + n))->v = strom_load_u64((const cl_uchar *)from + n);
+		for (; n < size; n++)
+			to[n] = from[n];
+		cl_uint		id = a.nkeys + r;
+		cl_ulong	h = textdict_hash((cl_ulong)from, a.blank_padded != 0);
+		entries[id].hash = h;
+		entries[id].off = at;
+		/* only lane i looks for PENDING | i in this slot: the others of this launch find a word
+		 * that is not theirs before and after this store */
+		__hip_atomic_store((textdict_slot_p)(slots + slot), textdict_tag(h) | id,
+						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_emit(keyunion_args a)
+{
+	const cl_ulong *slots = (const cl_ulong *)a.slots;
+	const cl_uint *key_slot = (const cl_uint *)a.key_slot;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	cl_int	   *map = (cl_int *)a.map;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < a.nimg; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		i = base + threadIdx.x;
+
+		if (i < a.nimg)
+		{
+			cl_uint		s = key_slot[i];
+			cl_ulong	w = (s < a.nslots ? slots[s] : 0UL);
+			cl_int		id = 0;
+
+			if ((w & TEXTDICT_OCCUPIED) == 0 || (w & TEXTDICT_PENDING) != 0 || (cl_uint)w >= a.nkeys)
+				errcode = StromError_SanityCheckViolation;
+			else
+				id = (cl_int)(cl_uint)w;
+			map[i] = id;
+		}
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+/* ids under one dictionary -> ids under another, in place; a NULL row's id becomes 0 without a
+ * look at the map (the dictionary the chunk was encoded under may hold no key at all) */
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+keyunion_recode(kern_data_store *chunk, keyunion_recode_args a)
+{
+	const kern_coldir *cd = KERN_DATA_STORE_COLDIR(chunk) + a.colidx;
+	cl_int	   *ids = (cl_int *)((char *)chunk + cd->values_off);
+	const cl_uint *notnull = (cd->nulls_off ? (const cl_uint *)((const char *)chunk + cd->nulls_off) : NULL);
+	const cl_int *map = (const cl_int *)a.map;
+	const cl_uint nrows = chunk->nitems;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < nrows; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		row = base + threadIdx.x;
+
+		if (row < nrows)
+		{
+			cl_int		id = 0;
+
+			if (!notnull || ((notnull[row >> 5] >> (row & 31)) & 1) != 0)
+			{
+				cl_uint		old = (cl_uint)ids[row];
+				if (old < a.mapsize)
+					id = map[old];
+				else
+					errcode = StromError_DataStoreCorruption;
+			}
+			ids[row] = id;
+		}
+	}
+	textdict_writeback_status((cl_int *)a.status, errcode);
 }
 
 #endif	/* STROM_TEXTDICT_DEVICE_H */

@@ -39,13 +39,21 @@ struct strom_textdict {
 	cl_uint		nkeys_hint = 0;
 	/* device time of the last encode's kernels, when the perfmon is on: probe, settle, emit, rebuild */
 	uint64_t	kern_ns[4] = {0, 0, 0, 0};
+	/* ... of the last absorb's (probe, ranks, settle, emit, rebuild) and of the last recode through one of
+	 * this dictionary's maps */
+	uint64_t	union_ns[6] = {0, 0, 0, 0, 0, 0};
 	/* the program the last encode ran: TEXTDICT_BLOCK / TEXTDICT_HASH_BITS are part of its text */
 	strom_devprog_key program = 0;
 };
 
 namespace {
 
-enum { K_PROBE = 0, K_SETTLE, K_EMIT, K_REBUILD };
+enum { K_PROBE = 0, K_SETTLE, K_EMIT, K_REBUILD,
+	   K_UPROBE, K_UCOUNT, K_UOFFSETS, K_USETTLE, K_UEMIT, K_RECODE, K_NFUNCS };
+enum { U_PROBE = 0, U_RANKS, U_SETTLE, U_EMIT, U_REBUILD, U_RECODE };
+const char *const kernel_names[K_NFUNCS] = {
+	"textdict_probe", "textdict_settle", "textdict_emit", "textdict_rebuild",
+	"keyunion_probe", "keyunion_count", "keyunion_offsets", "keyunion_settle", "keyunion_emit", "keyunion_recode" };
 
 /* the fixed program; the two knobs are part of its text (as build() pre-builds it) */
 std::string
@@ -106,17 +114,21 @@ pow2_at_least(size_t n)
 struct Encoder {
 	Device	   *dev;
 	hipStream_t	stream;
-	hipFunction_t fn[4];
+	hipFunction_t fn[K_NFUNCS];
 	unsigned	block;
 	unsigned	max_grid;
 	bool		timed;
+	uint64_t   *rebuild_ns;		/* where a rebuild's device time goes: the encode's or the absorb's account */
+
+	/* the fixed program's kernels first..last for this device, and the launch geometry */
+	int open(Device *device, int first, int last, strom_devprog_key *p_progkey);
 
 	unsigned grid_for(size_t n) const
 	{
 		return (unsigned)std::max<size_t>(1, std::min<size_t>((n + block - 1) / block, max_grid));
 	}
 
-	int launch(strom_textdict *dict, int which, unsigned grid, void **args)
+	int launch(uint64_t *acc, int which, unsigned grid, void **args)
 	{
 		hipEvent_t	ev0 = nullptr, ev1 = nullptr;
 		if (timed && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess))
@@ -130,7 +142,7 @@ struct Encoder {
 			(void)hipEventRecord(ev1, stream);
 			if (rc == hipSuccess && hipEventSynchronize(ev1) == hipSuccess &&
 				hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
-				dict->kern_ns[which] += (uint64_t)((double)ms * 1e6);
+				*acc += (uint64_t)((double)ms * 1e6);
 			(void)hipEventDestroy(ev0);
 			(void)hipEventDestroy(ev1);
 		}
@@ -188,7 +200,7 @@ struct Encoder {
 			return 0;
 		textdict_args a = base_args(dict);
 		void	   *args[] = { &a };
-		int			rc = launch(dict, K_REBUILD, grid_for(dict->nkeys), args);
+		int			rc = launch(rebuild_ns, K_REBUILD, grid_for(dict->nkeys), args);
 		textdict_ctl ctl;
 		if (rc == 0)
 			rc = read_ctl(dict, &ctl);
@@ -235,7 +247,7 @@ struct Encoder {
 
 			if (hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), stream) != hipSuccess)
 				return StromError_HipInternal;
-			if ((rc = launch(dict, K_PROBE, grid_for(nrows), args)) != 0 || (rc = read_ctl(dict, &ctl)) != 0)
+			if ((rc = launch(&dict->kern_ns[K_PROBE], K_PROBE, grid_for(nrows), args)) != 0 || (rc = read_ctl(dict, &ctl)) != 0)
 				return rc;
 			size_t	keys_after = (size_t)dict->nkeys + ctl.nnew;
 			/* no place found, or the claims took the table past half full; a row error goes first */
@@ -291,7 +303,7 @@ struct Encoder {
 			a.colidx = colidx;
 			a.nnew = nnew;
 			void	   *args[] = { &a_src, &a };
-			rc = launch(dict, K_SETTLE, grid_for(nnew), args);
+			rc = launch(&dict->kern_ns[K_SETTLE], K_SETTLE, grid_for(nnew), args);
 		}
 		if (rc == 0)
 		{
@@ -301,7 +313,7 @@ struct Encoder {
 			a.out_values = (cl_ulong)(uintptr_t)out_values;
 			a.out_notnull = (cl_ulong)(uintptr_t)out_notnull;
 			void	   *args[] = { &a_src, &a };
-			if ((rc = launch(dict, K_EMIT, grid_for(nrows), args)) == 0 && (rc = read_ctl(dict, &ctl)) == 0)
+			if ((rc = launch(&dict->kern_ns[K_EMIT], K_EMIT, grid_for(nrows), args)) == 0 && (rc = read_ctl(dict, &ctl)) == 0)
 				rc = ctl.status;				/* settle or emit met a word no launch writes */
 		}
 		if (rc != 0)
@@ -319,6 +331,29 @@ struct Encoder {
 		return 0;
 	}
 };
+
+int
+Encoder::open(Device *device, int first, int last, strom_devprog_key *p_progkey)
+{
+	int		errcode = 0;
+	Program *prog = textdict_program(&errcode, p_progkey);
+
+	dev = device;
+	stream = device->streams[0];
+	timed = perfmon_enabled();
+	rebuild_ns = nullptr;
+	for (int i = first; prog && i <= last; i++)
+		if (!(fn[i] = prog->get_function(device, kernel_names[i], &errcode)))
+			prog = nullptr;
+	if (!prog)
+		return errcode ? errcode : StromError_ProgramBuildFailure;
+	block = textdict_block();
+	max_grid = (unsigned)device->prop.multiProcessorCount * 8;
+	if (const char *v = getenv("STROM_TEXTDICT_MAX_GRID"))		/* tests: grid strides on small chunks */
+		if (atoi(v) > 0)
+			max_grid = (unsigned)atoi(v);
+	return 0;
+}
 
 void
 textdict_free(Device *dev, strom_textdict *dict)
@@ -546,26 +581,9 @@ strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, i
 	}
 	*p_errcode = 0;
 	Encoder	enc;
-	enc.dev = dev;
-	enc.stream = dev->streams[0];
-	enc.timed = perfmon_enabled();
-	int		errcode = 0;
 	strom_devprog_key progkey = 0;
-	Program *prog = textdict_program(&errcode, &progkey);
-	static const char *const names[4] = { "textdict_probe", "textdict_settle", "textdict_emit", "textdict_rebuild" };
-	for (int i = 0; prog && i < 4; i++)
-		if (!(enc.fn[i] = prog->get_function(dev, names[i], &errcode)))
-			prog = nullptr;
-	if (!prog)
-	{
-		*p_errcode = errcode ? errcode : StromError_ProgramBuildFailure;
+	if ((*p_errcode = enc.open(dev, K_PROBE, K_REBUILD, &progkey)) != 0)
 		return nullptr;
-	}
-	enc.block = textdict_block();
-	enc.max_grid = (unsigned)dev->prop.multiProcessorCount * 8;
-	if (const char *v = getenv("STROM_TEXTDICT_MAX_GRID"))		/* tests: grid strides on small chunks */
-		if (atoi(v) > 0)
-			enc.max_grid = (unsigned)atoi(v);
 
 	/* the encoded chunk: id columns (bitmap room always laid out, named in the directory only
 	 * when the column has a NULL), then the carried columns as they are */
@@ -622,6 +640,7 @@ strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, i
 		{
 			memset(dicts[i]->kern_ns, 0, sizeof(dicts[i]->kern_ns));
 			dicts[i]->program = progkey;
+			enc.rebuild_ns = &dicts[i]->kern_ns[K_REBUILD];
 			*p_errcode = enc.encode_column(dicts[i], src, (cl_uint)key_colidx[i], d_row_slot, d_newkeys,
 										   d_dst + cd[i].values_off, d_dst + nulls_at[i], &nnull[i]);
 		}
@@ -674,4 +693,421 @@ strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, i
 	if (!result && d_dst) dev->pool.release(d_dst);
 	return result;
 	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+/* ------------------------------------------------------------------ *
+ * union of dictionaries (devlib/strom_textdict.h: keyunion_*)
+ *
+ * One absorb:
+ *   probe -> read {status, nnew, toofull} -> NoSpace: grow, rebuild, probe again; another error:
+ *   rebuild at the same size and return it, as an encode does
+ *   count, offsets -> read the totals (the one other small copy) -> room for entries and heap
+ *   settle, emit -> read status -> the counters move
+ * ------------------------------------------------------------------ */
+struct strom_keymap {
+	strom_textdict *dst = nullptr;
+	int			dindex = 0;
+	cl_uint		n = 0;
+	cl_int	   *ids = nullptr;			/* device: int4[n] */
+	cl_int	   *status = nullptr;		/* device: the word a recode reports through */
+};
+
+namespace {
+
+void
+keymap_free(Device *dev, strom_keymap *map)
+{
+	if (map->ids) dev->pool.release(map->ids);
+	if (map->status) dev->pool.release(map->status);
+	delete map;
+}
+
+/* the image lies on the device: heap[heaplen], key i at the offset found at offsets + i * stride */
+strom_keymap *
+absorb_image(Device *dev, strom_textdict *dst, const char *d_heap, size_t heaplen,
+			 const void *d_offsets, cl_uint stride, cl_uint nimg, int *p_errcode)
+{
+	Encoder		enc;
+	strom_devprog_key progkey = 0;
+	int			rc;
+
+	if ((*p_errcode = enc.open(dev, K_REBUILD, K_UEMIT, &progkey)) != 0)
+		return nullptr;
+	memset(dst->union_ns, 0, sizeof(uint64_t) * U_RECODE);
+	enc.rebuild_ns = &dst->union_ns[U_REBUILD];
+	dst->program = progkey;
+
+	strom_keymap *map = new strom_keymap();
+	map->dst = dst;
+	map->dindex = dst->dindex;
+	map->n = nimg;
+	map->ids = (cl_int *)dev->pool.alloc(sizeof(cl_int) * std::max<size_t>(nimg, 1));
+	map->status = (cl_int *)dev->pool.alloc(sizeof(cl_int));
+	cl_uint		ntiles = (cl_uint)(((size_t)nimg + enc.block - 1) / enc.block);
+	cl_uint	   *d_key_slot = (cl_uint *)dev->pool.alloc(sizeof(cl_uint) * std::max<size_t>(nimg, 1));
+	keyunion_tile *d_tiles = (keyunion_tile *)dev->pool.alloc(sizeof(keyunion_tile) * ((size_t)ntiles + 1));
+	bool		touched = false;			/* the slot array may hold claims of this call */
+
+	auto args_of = [&](void) {
+		keyunion_args a;
+		memset(&a, 0, sizeof(a));
+		a.slots = (cl_ulong)(uintptr_t)dst->slots;
+		a.entries = (cl_ulong)(uintptr_t)dst->entries;
+		a.heap = (cl_ulong)(uintptr_t)dst->heap;
+		a.ctl = (cl_ulong)(uintptr_t)dst->ctl;
+		a.img_heap = (cl_ulong)(uintptr_t)d_heap;
+		a.img_offsets = (cl_ulong)(uintptr_t)d_offsets;
+		a.img_heaplen = heaplen;
+		a.key_slot = (cl_ulong)(uintptr_t)d_key_slot;
+		a.tiles = (cl_ulong)(uintptr_t)d_tiles;
+		a.map = (cl_ulong)(uintptr_t)map->ids;
+		a.heap_usage = dst->heap_usage;
+		a.heap_size = dst->heap_size;
+		a.img_stride = stride;
+		a.nimg = nimg;
+		a.ntiles = ntiles;
+		a.nslots = dst->nslots;
+		a.nkeys = dst->nkeys;
+		a.blank_padded = dst->blank_padded ? 1 : 0;
+		return a;
+	};
+
+	rc = (!map->ids || !map->status || !d_key_slot || !d_tiles) ? StromError_OutOfMemory : 0;
+	textdict_ctl ctl;
+	keyunion_tile total;
+	memset(&ctl, 0, sizeof(ctl));
+	memset(&total, 0, sizeof(total));
+	for (int turn = 0; rc == 0 && nimg > 0; turn++)
+	{
+		keyunion_args a = args_of();
+		void	   *args[] = { &a };
+
+		if (hipMemsetAsync(dst->ctl, 0, sizeof(textdict_ctl), enc.stream) != hipSuccess)
+		{
+			rc = StromError_HipInternal;
+			break;
+		}
+		touched = true;
+		if ((rc = enc.launch(&dst->union_ns[U_PROBE], K_UPROBE, enc.grid_for(nimg), args)) != 0 ||
+			(rc = enc.read_ctl(dst, &ctl)) != 0)
+			break;
+		size_t	keys_after = (size_t)dst->nkeys + ctl.nnew;
+		bool	nospace = (ctl.status == StromError_DataStoreNoSpace || (ctl.status == 0 && ctl.toofull != 0));
+
+		if (ctl.status != 0 && !nospace)
+		{
+			rc = ctl.status;				/* a key of the image is broken: nothing of it stays */
+			break;
+		}
+		if (!nospace)
+			break;
+		if (turn >= 40 || keys_after >= ((size_t)1 << 29))
+		{
+			rc = StromError_DataStoreNoSpace;
+			break;
+		}
+		cl_uint	nslots = std::max(pow2_at_least(4 * keys_after), pow2_at_least(8 * (size_t)dst->nslots));
+		rc = enc.rebuild(dst, nslots);		/* drops the claims; the next turn probes again */
+	}
+	if (rc == 0 && nimg > 0)
+	{
+		/* which keys are new, in image order, and what they need */
+		keyunion_args a = args_of();
+		void	   *args[] = { &a };
+
+		if ((rc = enc.launch(&dst->union_ns[U_RANKS], K_UCOUNT, std::min(ntiles, enc.max_grid), args)) == 0 &&
+			(rc = enc.launch(&dst->union_ns[U_RANKS], K_UOFFSETS, 1, args)) == 0 &&
+			(hipMemcpyAsync(&total, d_tiles + ntiles, sizeof(total), hipMemcpyDeviceToHost, enc.stream) != hipSuccess ||
+			 hipStreamSynchronize(enc.stream) != hipSuccess))
+			rc = StromError_HipInternal;
+		if (rc == 0 && (rc = enc.read_ctl(dst, &ctl)) == 0 && ctl.status != 0)
+			rc = ctl.status;
+		if (rc == 0 && total.count != ctl.nnew)
+			rc = StromError_SanityCheckViolation;			/* every claim is one new key */
+		size_t	keys_after = (size_t)dst->nkeys + total.count;
+		if (rc == 0 && keys_after >= ((size_t)1 << 29))
+			rc = StromError_DataStoreNoSpace;
+		/* entries and heap are not what the slot words name: they grow without another probe */
+		if (rc == 0 && keys_after > dst->entries_cap)
+		{
+			size_t	need = std::max(keys_after, 2 * (size_t)dst->entries_cap);
+			if ((rc = enc.grow(&dst->entries, dst->nkeys, need)) == 0)
+				dst->entries_cap = (cl_uint)need;
+		}
+		if (rc == 0 && dst->heap_usage + total.bytes > dst->heap_size)
+		{
+			size_t	need = std::max(dst->heap_usage + (size_t)total.bytes, 2 * dst->heap_size);
+			if ((rc = enc.grow(&dst->heap, dst->heap_usage, need)) == 0)
+				dst->heap_size = need;
+		}
+	}
+	if (rc == 0 && nimg > 0)
+	{
+		keyunion_args a = args_of();
+		void	   *args[] = { &a };
+
+		if (total.count > 0)
+			rc = enc.launch(&dst->union_ns[U_SETTLE], K_USETTLE, std::min(ntiles, enc.max_grid), args);
+		a.nkeys = dst->nkeys + total.count;
+		if (rc == 0 && (rc = enc.launch(&dst->union_ns[U_EMIT], K_UEMIT, enc.grid_for(nimg), args)) == 0 &&
+			(rc = enc.read_ctl(dst, &ctl)) == 0)
+			rc = ctl.status;
+	}
+	(void)hipStreamSynchronize(enc.stream);
+	if (rc == 0)
+	{
+		dst->nkeys += total.count;
+		dst->heap_usage += total.bytes;
+		if (2 * (size_t)dst->nkeys > dst->nslots)
+			rc = enc.rebuild(dst, pow2_at_least(4 * (size_t)dst->nkeys));
+	}
+	else if (touched && dst->slots)
+		(void)enc.rebuild(dst, dst->nslots);	/* back to the keys before the call: entries below nkeys */
+	if (d_key_slot) dev->pool.release(d_key_slot);
+	if (d_tiles) dev->pool.release(d_tiles);
+	if (rc != 0)
+	{
+		keymap_free(dev, map);
+		*p_errcode = rc;
+		return nullptr;
+	}
+	return map;
+}
+
+/* a host image before any launch: every datum inside the heap by its own length, with a header
+ * the device reads in place */
+bool
+host_image_is_sound(const unsigned char *heap, size_t heaplen, const uint64_t *offsets, uint32_t nkeys)
+{
+	for (uint32_t i = 0; i < nkeys; i++)
+	{
+		uint64_t	off = offsets[i];
+		if (off >= heaplen)
+			return false;
+		unsigned char b0 = heap[off];
+		if (b0 == 0x01 || (b0 & 0x03) == 0x02)
+			return false;
+		uint64_t	size;
+		if (b0 & 0x01)
+			size = (b0 >> 1) & 0x7f;
+		else
+		{
+			if (off + 4 > heaplen)
+				return false;
+			uint32_t w = (uint32_t)heap[off] | ((uint32_t)heap[off + 1] << 8) |
+				((uint32_t)heap[off + 2] << 16) | ((uint32_t)heap[off + 3] << 24);
+			size = (w >> 2) & 0x3fffffff;
+		}
+		if (size < ((b0 & 0x01) ? 1u : 4u) || off + size > heaplen)
+			return false;
+	}
+	return true;
+}
+
+}	/* namespace */
+
+extern "C" strom_keymap *
+strom_keyunion_absorb(strom_textdict *dst, const void *heap, size_t heaplen,
+					  const uint64_t *offsets, uint32_t nkeys, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = StromError_BadRequestMessage;
+	if (!dst || nkeys > (1u << 28) || (nkeys > 0 && (!heap || !offsets)))
+		return nullptr;
+	Device *dev = get_device(dst->dindex);
+	if (!dev)
+	{
+		*p_errcode = StromError_ServerNotReady;
+		return nullptr;
+	}
+	if (!host_image_is_sound((const unsigned char *)heap, heaplen, offsets, nkeys))
+	{
+		*p_errcode = StromError_DataStoreCorruption;
+		return nullptr;
+	}
+	(void)hipSetDevice(dev->hip_id);
+	*p_errcode = 0;
+	char	   *d_heap = nullptr;
+	uint64_t   *d_offsets = nullptr;
+	if (nkeys > 0)
+	{
+		d_heap = (char *)dev->pool.alloc(heaplen);
+		d_offsets = (uint64_t *)dev->pool.alloc(sizeof(uint64_t) * nkeys);
+		if (!d_heap || !d_offsets)
+			*p_errcode = StromError_OutOfMemory;
+		else if (hipMemcpyAsync(d_heap, heap, heaplen, hipMemcpyHostToDevice, dev->streams[0]) != hipSuccess ||
+				 hipMemcpyAsync(d_offsets, offsets, sizeof(uint64_t) * nkeys, hipMemcpyHostToDevice,
+								dev->streams[0]) != hipSuccess ||
+				 hipStreamSynchronize(dev->streams[0]) != hipSuccess)
+			*p_errcode = StromError_HipInternal;
+	}
+	strom_keymap *map = nullptr;
+	if (*p_errcode == 0)
+		map = absorb_image(dev, dst, d_heap, heaplen, d_offsets, sizeof(uint64_t), nkeys, p_errcode);
+	if (d_heap) dev->pool.release(d_heap);
+	if (d_offsets) dev->pool.release(d_offsets);
+	return map;
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+extern "C" strom_keymap *
+strom_keyunion_absorb_dict(strom_textdict *dst, strom_textdict *src, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = StromError_BadRequestMessage;
+	if (!dst || !src || dst == src || dst->type_oid != src->type_oid || dst->dindex != src->dindex)
+		return nullptr;
+	Device *dev = get_device(dst->dindex);
+	if (!dev)
+	{
+		*p_errcode = StromError_ServerNotReady;
+		return nullptr;
+	}
+	(void)hipSetDevice(dev->hip_id);
+	*p_errcode = 0;
+	/* src's heap and the 'off' words of its entries are the image, where they lie */
+	return absorb_image(dev, dst, src->heap, src->heap_usage, &src->entries[0].off,
+						sizeof(textdict_entry), src->nkeys, p_errcode);
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+extern "C" uint32_t
+strom_keymap_size(strom_keymap *map)
+{
+	return map ? map->n : 0;
+}
+
+extern "C" int
+strom_keymap_fetch(strom_keymap *map, int32_t *out, size_t n)
+{
+	if (!map || (!out && map->n > 0))
+		return StromError_BadRequestMessage;
+	if (n < map->n)
+		return StromError_DataStoreNoSpace;
+	Device *dev = get_device(map->dindex);
+	if (!dev)
+		return StromError_ServerNotReady;
+	(void)hipSetDevice(dev->hip_id);
+	if (map->n > 0 && hipMemcpy(out, map->ids, sizeof(cl_int) * map->n, hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_HipInternal;
+	return 0;
+}
+
+extern "C" void
+strom_keymap_release(strom_keymap *map)
+{
+	if (!map)
+		return;
+	Device *dev = get_device(map->dindex);
+	if (dev)
+	{
+		(void)hipSetDevice(dev->hip_id);
+		(void)hipStreamSynchronize(dev->streams[0]);
+		keymap_free(dev, map);
+	}
+	else
+		delete map;
+}
+
+extern "C" int
+strom_keyunion_kernel_ns(strom_textdict *dst, uint64_t *ns_out)
+{
+	if (!dst || !ns_out)
+		return StromError_BadRequestMessage;
+	memcpy(ns_out, dst->union_ns, sizeof(dst->union_ns));
+	return 0;
+}
+
+extern "C" int
+strom_keyunion_recode(strom_dstore *encoded, const int32_t *colidx, strom_keymap *const *maps, int ncols)
+{
+	STROM_ABI_TRY
+	if (!encoded || !colidx || !maps || ncols < 1 || ncols > STROM_PREAGG_MAXKEYS)
+		return StromError_BadRequestMessage;
+	if (encoded->head.format != KDS_FORMAT_COLUMN || encoded->head.ncols < 1 || encoded->head.ncols > 1600)
+		return StromError_BadRequestMessage;
+	int		chunk_ncols = (int)encoded->head.ncols;
+	for (int i = 0; i < ncols; i++)
+	{
+		if (!maps[i] || maps[i]->dindex != encoded->dindex || colidx[i] < 0 || colidx[i] >= chunk_ncols)
+			return StromError_BadRequestMessage;
+		for (int j = 0; j < i; j++)
+			if (colidx[j] == colidx[i])
+				return StromError_BadRequestMessage;		/* a column is recoded once */
+	}
+	Device *dev = get_device(encoded->dindex);
+	if (!dev)
+		return StromError_ServerNotReady;
+	(void)hipSetDevice(dev->hip_id);
+	std::vector<char> hbuf(KDS_COLUMN_HEAD_LENGTH(chunk_ncols), 0);
+	if (hbuf.size() > encoded->length)
+		return StromError_BadRequestMessage;
+	if (hipMemcpy(hbuf.data(), encoded->devptr, hbuf.size(), hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_HipInternal;
+	const kern_data_store *head = (const kern_data_store *)hbuf.data();
+	kern_coldir *cd = KERN_DATA_STORE_COLDIR(head);
+	cl_uint	nrows = encoded->head.nitems;
+	size_t	bitmap_len = sizeof(cl_uint) * (((size_t)nrows + 31) / 32);
+	for (int i = 0; i < ncols; i++)
+	{
+		const kern_colmeta *cm = &head->colmeta[colidx[i]];
+		if (cm->attlen != 4 || !cm->attbyval)
+			return StromError_BadRequestMessage;			/* not a column of int4 ids */
+		if ((size_t)cd[colidx[i]].values_off + sizeof(cl_int) * (size_t)nrows > encoded->length ||
+			(cd[colidx[i]].nulls_off != 0 && (size_t)cd[colidx[i]].nulls_off + bitmap_len > encoded->length))
+			return StromError_DataStoreCorruption;
+	}
+	Encoder	enc;
+	strom_devprog_key progkey = 0;
+	int		rc = enc.open(dev, K_RECODE, K_RECODE, &progkey);
+	if (rc != 0)
+		return rc;
+	for (int i = 0; i < ncols; i++)
+		maps[i]->dst->union_ns[U_RECODE] = 0;
+	for (int i = 0; i < ncols && rc == 0; i++)
+	{
+		strom_keymap *map = maps[i];
+		const void *a_chunk = encoded->devptr;
+		keyunion_recode_args a;
+		memset(&a, 0, sizeof(a));
+		a.map = (cl_ulong)(uintptr_t)map->ids;
+		a.status = (cl_ulong)(uintptr_t)map->status;
+		a.mapsize = map->n;
+		a.colidx = (cl_uint)colidx[i];
+		void	   *args[] = { &a_chunk, &a };
+		cl_int		status = 0;
+
+		if (hipMemsetAsync(map->status, 0, sizeof(cl_int), enc.stream) != hipSuccess)
+			rc = StromError_HipInternal;
+		else if ((rc = enc.launch(&map->dst->union_ns[U_RECODE], K_RECODE, enc.grid_for(nrows), args)) == 0)
+		{
+			if (hipMemcpyAsync(&status, map->status, sizeof(status), hipMemcpyDeviceToHost, enc.stream) != hipSuccess ||
+				hipStreamSynchronize(enc.stream) != hipSuccess)
+				rc = StromError_HipInternal;
+			else
+				rc = status;
+		}
+		/* the ids' new domain */
+		kern_coldir *c = &cd[colidx[i]];
+		cl_uint		nk = map->dst->nkeys;
+		if (rc == 0 && nk > 0 && (c->stat_flags & KDS_COLSTAT_MINMAX) != 0)
+		{
+			c->minval = 0;
+			c->maxval = (cl_long)nk - 1;
+			if (hipMemcpy((char *)encoded->devptr + ((const char *)c - hbuf.data()), c, sizeof(*c),
+						  hipMemcpyHostToDevice) != hipSuccess)
+				rc = StromError_HipInternal;
+		}
+	}
+	if (rc != 0)
+		(void)hipStreamSynchronize(enc.stream);
+	encoded->coldir.reset();				/* the host's snapshot of the zone maps is of the old ids */
+	return rc;
+	STROM_ABI_CATCH(StromError_OutOfMemory, (int *)nullptr)
 }

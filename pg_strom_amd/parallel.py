@@ -369,3 +369,19 @@ def gather_partial_rows(targets, values, isnull, group=None):
     parts = [None] * world
     dist.all_gather_object(parts, (np.ascontiguousarray(values), np.ascontiguousarray(isnull)), group=group)
     return merge_partial_rows(targets, parts)
+
+
+# ---------------------------------------------------------------------------
+# GROUP BY text: the ranks' key dictionaries number their keys independently.  Before the first
+# fold every rank learns every rank's key image and absorbs them in rank order
+# (textdict.TextDictionary.absorb): the union dictionaries then agree id for id, and the merges
+# above apply to sessions over text ids as they do to any fixed-width key.
+# ---------------------------------------------------------------------------
+def allgather_key_images(image, group=None):
+    """image: (heap bytes, offsets) of this rank's dictionary (TextDictionary.image()).  Returns
+    every rank's image, in rank order, on every rank."""
+    import torch.distributed as dist
+    heap, offsets = image
+    images = [None] * dist.get_world_size(group)
+    dist.all_gather_object(images, (bytes(heap), np.ascontiguousarray(offsets, dtype=np.uint64)), group=group)
+    return images

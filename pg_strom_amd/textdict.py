@@ -7,6 +7,13 @@ Here a dictionary of its own (strom_textdict_*, devlib/strom_textdict.h) maps th
 of a resident COLUMN chunk to dense int4 ids; GpuPreAgg groups the encoded chunk by
 (key (var K int4)) and the ids are replaced by their keys after the fetch.  group_by_text() is
 the executor loop a backend would write.
+
+Several shards (row ranges of one table, one process per GPU) each have a dictionary of their own,
+and their sessions can only be merged when they call the same key by the same id: unify() builds
+the union dictionary every rank builds alike (strom_keyunion_*: new keys are numbered in the order
+of the key images, not in the order lanes win a slot), recode() rewrites the id columns of the
+encoded chunks through the id maps, and group_by_text_sharded() is that loop with shards of one
+device standing in for ranks.
 """
 import ctypes
 import os
@@ -67,6 +74,49 @@ class TextDictionary(object):
             raise runtime.StromError(err.value, "strom_textdict_encode")
         return runtime.DeviceStore(h, store.nitems)
 
+    def image(self):
+        """the keys as they lie in the dictionary: (heap bytes, offsets[id] of each complete datum) --
+        what another dictionary absorbs, on this rank or on another"""
+        nbytes = ctypes.c_size_t(0)
+        n = lib.strom_textdict_fetch(self.handle, None, 0, None, 0, ctypes.byref(nbytes))
+        if n < 0:
+            raise runtime.StromError(-n, "strom_textdict_fetch")
+        heap = np.zeros(max(nbytes.value, 1), dtype=np.uint8)
+        offs = np.zeros(max(n, 1), dtype=np.uint64)
+        n = lib.strom_textdict_fetch(self.handle, heap.ctypes.data, len(heap), offs.ctypes.data, len(offs),
+                                     ctypes.byref(nbytes))
+        if n < 0:
+            raise runtime.StromError(-n, "strom_textdict_fetch")
+        return heap[:nbytes.value].tobytes(), offs[:n].copy()
+
+    def absorb(self, image):
+        """image: (heap bytes, offsets) as image() returns it.  Its keys enter this dictionary, new ones
+        numbered in image order; returns the KeyMap: id in the image -> id here"""
+        heap, offs = image
+        heap = np.frombuffer(bytes(heap), dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        err = ctypes.c_int(0)
+        h = lib.strom_keyunion_absorb(self.handle, heap.ctypes.data if len(heap) else None, len(heap),
+                                      offs.ctypes.data if len(offs) else None, len(offs), ctypes.byref(err))
+        if not h:
+            raise runtime.StromError(err.value, "strom_keyunion_absorb")
+        return KeyMap(h, self)
+
+    def absorb_dict(self, other):
+        """absorb(other.image()) without the way over the host: both dictionaries are on one device"""
+        err = ctypes.c_int(0)
+        h = lib.strom_keyunion_absorb_dict(self.handle, other.handle, ctypes.byref(err))
+        if not h:
+            raise runtime.StromError(err.value, "strom_keyunion_absorb_dict")
+        return KeyMap(h, self)
+
+    def union_kernel_ns(self):
+        """device time of the last absorb's kernels and of the last recode through one of this dictionary's
+        maps (runtime perfmon on)"""
+        ns = (ctypes.c_uint64 * 6)()
+        lib.strom_keyunion_kernel_ns(self.handle, ns)
+        return dict(zip(("probe", "ranks", "settle", "emit", "rebuild", "recode"), [int(v) for v in ns]))
+
     def keys(self):
         """payload bytes of every key, by id (header stripped; character(n) without its padding)"""
         nbytes = ctypes.c_size_t(0)
@@ -109,6 +159,126 @@ class TextDictionary(object):
         if self.handle:
             lib.strom_textdict_release(self.handle)
             self.handle = None
+
+
+class KeyMap(object):
+    """device-resident id map of one absorb: id under the absorbed image -> id under 'dictionary'.
+    Release it before the dictionary."""
+
+    def __init__(self, handle, dictionary):
+        self.handle = handle
+        self.dictionary = dictionary
+
+    def __len__(self):
+        return lib.strom_keymap_size(self.handle)
+
+    def ids(self):
+        out = np.zeros(max(len(self), 1), dtype=np.int32)
+        rc = lib.strom_keymap_fetch(self.handle, out.ctypes.data, len(out))
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_keymap_fetch")
+        return out[:len(self)]
+
+    def release(self):
+        if self.handle:
+            lib.strom_keymap_release(self.handle)
+            self.handle = None
+
+
+def recode(enc, cols, maps):
+    """the int4 id columns 'cols' (0-based) of the encoded chunk 'enc' through 'maps', in place"""
+    assert len(cols) == len(maps)
+    colidx = (ctypes.c_int32 * max(len(cols), 1))(*[int(c) for c in cols])
+    handles = (ctypes.c_void_p * max(len(maps), 1))(*[m.handle for m in maps])
+    rc = lib.strom_keyunion_recode(enc.handle, colidx, handles, len(cols))
+    if rc != 0:
+        raise runtime.StromError(rc, "strom_keyunion_recode")
+
+
+def unify(dicts, dindex=0):
+    """(G, maps): a fresh dictionary that has absorbed each of 'dicts' in order, and per dictionary the
+    map of its ids to G's.  Ranks that absorb the same dictionaries' images in the same order
+    (G.absorb(image) for the images of parallel.allgather_key_images) get the same G."""
+    union = TextDictionary(dicts[0].kind, nkeys_hint=min(sum(d.num_keys for d in dicts), 1 << 28), dindex=dindex)
+    maps = []
+    try:
+        for d in dicts:
+            maps.append(union.absorb_dict(d))
+    except Exception:
+        for m in maps:
+            m.release()
+        union.release()
+        raise
+    return union, maps
+
+
+def group_by_text_sharded(shards, text_keys, spec, carry_cols, hashed=False, int_keys=()):
+    """GROUP BY over text / character(n) keys of a table that lies in shards, one session per shard:
+    the multi-rank loop, with shards of ONE device standing in for ranks (real ranks exchange their
+    key images with parallel.allgather_key_images and absorb them in rank order instead of calling
+    unify(); the session merge is then strom_gpupreagg_allreduce / _reduce_scatter).
+
+    shards     [[resident COLUMN chunks of shard r]]; the other arguments as group_by_text's
+    Returns (PartialRows of the merged sessions, key columns) as group_by_text does.
+    """
+    key_cols = [c for c, _ in text_keys]
+    own = [[TextDictionary(kind) for _, kind in text_keys] for _ in shards]
+    unions, maps = [], []               # per text key: G, [KeyMap of shard r]
+    encoded = [[] for _ in shards]
+    sessions = []
+    try:
+        # 1. every shard under dictionaries of its own
+        for r, chunks in enumerate(shards):
+            for chunk in chunks:
+                encoded[r].append(own[r][0].encode(chunk, key_cols, carry_cols, own[r]))
+        # 2. one union dictionary per text key, the shards' keys in rank order
+        for k in range(len(text_keys)):
+            g, m = unify([own[r][k] for r in range(len(shards))])
+            unions.append(g)
+            maps.append(m)
+        # 3. the id columns into the common numbering
+        for r in range(len(shards)):
+            for enc in encoded[r]:
+                recode(enc, list(range(len(text_keys))), [maps[k][r] for k in range(len(text_keys))])
+        # 4. one session per shard over the common domain
+        domain = None
+        if not hashed:
+            domain = [(0, g.num_keys) for g in unions]
+            if int_keys:
+                ncols = len(key_cols) + len(carry_cols)
+                domain += domain_of([_chunk_head(e, ncols) for es in encoded for e in es], list(int_keys))
+        for r in range(len(shards)):
+            agg = GpuPreAgg(spec)
+            sessions.append(agg)
+            if hashed:
+                agg.begin_hashed()
+            else:
+                assert len(domain) == sum(1 for k, _ in agg.targets if k == KIND_KEY), \
+                    "every key target needs a domain: text_keys + int_keys"
+                agg.begin(domain)
+            for enc in encoded[r]:
+                status, _ = agg.fold(enc)
+                if status != 0:
+                    raise runtime.StromError(status, "GpuPreAgg fold")
+        # 5. the merge the ranks would run as a collective
+        if hashed:
+            GpuPreAgg.exchange_local(sessions, gather_after=True)
+        else:
+            for other in sessions[1:]:
+                sessions[0].merge_from(other)
+        pr = sessions[0].fetch()
+        return pr, ids_to_keys(pr, unions)
+    finally:
+        for agg in sessions:
+            agg.end()
+        for es in encoded:
+            for e in es:
+                e.release()
+        for ms in maps:
+            for m in ms:
+                m.release()
+        for d in unions + [d for ds in own for d in ds]:
+            d.release()
 
 
 def group_by_text(chunks, text_keys, spec, carry_cols, hashed=False, row_maps=None, dicts=None, int_keys=()):

@@ -526,6 +526,44 @@ strom_task *strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
 										  const int32_t *type_oids,
 										  strom_done_cb done, void *arg, int *p_errcode);
 
+/*
+ * ... and a STAR of such lookups in the same single pass (gpupreagg_dense_lookup_star):
+ * "fact JOIN dim1 JOIN dim2 ... GROUP BY".  tbls[d - 1] is relation d (1-based), each a table
+ * as strom_submit_gpupreagg_lookup takes it (one inner relation, DIRECT index, unique keys, joined
+ * on the plain outer column its own join program names, no pulled-up qual in that program).
+ * src_depth[i] is 0 .. ntbls: 0 an outer column, d column src_colidx[i] of relation d.  An inner
+ * join over all relations: a row is folded only if EVERY relation has a partner for it (key not
+ * NULL, inside the table's key range, slot present); the WHERE is the aggregate program's (qual
+ * ...), evaluated before any probe when it reads outer columns only, and an error in it is raised
+ * only for a row that has a partner in every relation.
+ * Two fact columns that point at the SAME dimension are two tables: a table's program names one
+ * outer column, so the dimension is built once per fact column that joins it.
+ * ntbls == 1 is strom_submit_gpupreagg_lookup.  BadRequest, and nothing is launched: ntbls
+ * outside 1 .. STROM_LOOKUP_STAR_MAXRELS, a depth outside 0 .. ntbls, a table that fails the
+ * requirements above or lives on another device, a hashed session, a session without a domain, a
+ * program with varlena variables, a key that is not 4 or 8 bytes wide, and for ntbls >= 2 a
+ * relation whose slot record is longer than 16 bytes or records that total more than 32 bytes
+ * over all relations (the kernel holds a row's records of all relations in registers): the
+ * caller then goes through the plain join and strom_hashjoin_project_column().
+ */
+#define STROM_LOOKUP_STAR_MAXRELS	4
+strom_task *strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
+											   strom_hashjoin_table *const *tbls, int ntbls,
+											   strom_dstore *outer,
+											   int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+											   const int32_t *type_oids,
+											   strom_done_cb done, void *arg, int *p_errcode);
+/*
+ * The define block the runtime puts in front of a session's source to build the star kernels for
+ * a mapping (no device needed: a planner or a test can compile the program ahead): relation d
+ * (1-based) has a key of keylen[d-1] bytes, slot records of reclen[d-1] bytes in the narrow form
+ * or not, and serves the virtual columns in inner_mask[d-1] (bit i: column i).  Returns the
+ * length of the text, or -1 if it does not fit buflen or describes no valid mapping.
+ */
+int			strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+												const int32_t *narrow, const uint64_t *inner_mask,
+												char *buf, size_t buflen);
+
 /* ------------------------------------------------------------------ *
  * chained operators: device-resident row maps
  *

@@ -171,6 +171,41 @@ struct gpupreagg_joined_map {
 };
 static_assert(sizeof(gpupreagg_joined_map) == 2600, "gpupreagg_joined_map");
 
+/*
+ * the virtual joined relation of gpupreagg_dense_lookup_star / _packed_lookup_star: a star of
+ * relations 1 .. nrels, each a DIRECT unique-key table probed by an outer column of its own; a
+ * virtual column of depth d comes from relation d's slot record.  What is a fact of the mapping
+ * (the relation count, per relation the record length and form, the key's width and which columns
+ * it serves) is ALSO compiled into the program (GPUPREAGG_STAR_*): the kernel reads the rest here.
+ */
+#define GPUPREAGG_STAR_MAXRELS		4		/* == STROM_LOOKUP_STAR_MAXRELS of strom_hip.h */
+#define GPUPREAGG_STAR_MAXRECLEN	16		/* one relation's slot record, two relations and more */
+#define GPUPREAGG_STAR_MAXRECBYTES	32		/* ... and all relations' records of a row together */
+struct gpupreagg_star_map {
+	cl_uint		ncols;
+	cl_uint		nrels;
+	struct {
+		cl_int		key_col;		/* outer column (0-based) that is this relation's join key */
+		cl_int		key_attlen;		/* 4 or 8 */
+		cl_uint		nslots;
+		cl_uint		reclen;			/* 2 / 4 (narrow), 8 or 16 */
+		cl_long		key_min;
+		cl_ulong	recs;			/* device address of the slot records */
+		cl_uint		narrow;
+		cl_uint		__pad;
+	} rel[GPUPREAGG_STAR_MAXRELS];
+	struct {
+		cl_int		depth;			/* 0: outer column 'col'; d: column 'col' of relation d */
+		cl_int		col;
+		cl_uint		recoff;			/* standard records: byte offset of the value in the record */
+		cl_uint		nullbit;		/* its bit in the record's flags word */
+		cl_uint		nshift;			/* narrow records: value = nmin + ((word >> nshift) & nmask) */
+		cl_uint		nmask;
+		cl_long		nmin;
+	} c[GPUPREAGG_JOINED_MAXCOLS];
+};
+static_assert(sizeof(gpupreagg_star_map) == 2216, "gpupreagg_star_map");
+
 /* key range of one chunk (gpupreagg_keyrange), read back by the host */
 struct gpupreagg_keyrange_t {
 	cl_long		kmin[GPUPREAGG_MAXKEYS];

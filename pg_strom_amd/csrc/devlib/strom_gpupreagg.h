@@ -1959,6 +1959,434 @@ gpupreagg_packed_lookup(kern_gpupreagg *kgpreagg,
 #endif
 
 /* ====================================================================== *
+ * star join as lookups + dense-id reduction in ONE pass over the outer chunk
+ *
+ * "fact JOIN dim1 JOIN dim2 ... GROUP BY": relations 1 .. GPUPREAGG_STAR_NRELS, each a table as
+ * gpupreagg_dense_lookup takes ONE of (DIRECT index, unique keys, packed slot records), each
+ * probed by an outer column of its own.  An inner join: a row is folded only if every relation
+ * has a partner; a virtual column of depth d comes from relation d's slot record.
+ *
+ * These kernels exist only in a program built FOR the mapping (gpupreagg.cpp:
+ * star_mapping_program): the relation count and per relation GPUPREAGG_STAR_RECLEN_<d> /
+ * _NARROW_<d> / _KEYLEN_<d> / _INNER_MASK_<d> (bit i: virtual column i is served by relation d)
+ * are compile-time constants; there is no run-time-mapping form.
+ *
+ * What gpupreagg_dense_lookup_body learned holds here: a slot record is ONE global load, every
+ * probe of the tile is issued before the first is used, dead rows look at slot 0, the
+ * bitmap-free loader.  What differs is the register file: at 1024 threads a wave has 128 VGPRs,
+ * the one-relation kernel sits at 123 with its next-tile prefetch, and every further relation adds
+ * a streamed key column, its slots and its record words.  So
+ *   - there is no next-tile prefetch (no Tnext, no second set of key quads);
+ *   - a relation's keys die into a 32-bit slot per row (an int8 key halves there) before any
+ *     probe is issued, and "dead" is decided from the keys and the qual-first alone -- never from
+ *     another relation's record, which would chain the relations' round trips;
+ *   - the relations' records (<= GPUPREAGG_STAR_MAXRECBYTES bytes per row over all of them: the
+ *     host refuses more) are decoded relation after relation into the tile T and the 'gone' bits,
+ *     the words of one dying before the next one's are unpacked.
+ * profiles/star_lookup_resources.txt has the registers per mapping.
+ * ====================================================================== */
+#if defined(GPUPREAGG_STAR_NRELS)
+#if GPUPREAGG_STAR_NRELS < 1 || GPUPREAGG_STAR_NRELS > GPUPREAGG_STAR_MAXRELS
+#error "GPUPREAGG_STAR_NRELS: 1 .. GPUPREAGG_STAR_MAXRELS relations"
+#endif
+#if GPUPREAGG_STAR_NRELS == 1
+#define GPUPREAGG_STAR_REL_LIST(M)	M(1)
+#elif GPUPREAGG_STAR_NRELS == 2
+#define GPUPREAGG_STAR_REL_LIST(M)	M(1) M(2)
+#elif GPUPREAGG_STAR_NRELS == 3
+#define GPUPREAGG_STAR_REL_LIST(M)	M(1) M(2) M(3)
+#else
+#define GPUPREAGG_STAR_REL_LIST(M)	M(1) M(2) M(3) M(4)
+#endif
+
+template <int KEYLEN> struct gpupreagg_star_key { typedef cl_int type; };
+template <> struct gpupreagg_star_key<8> { typedef cl_long type; };
+
+/* the compile-time facts of relation R */
+template <int R> struct gpupreagg_star_rel;
+#define GPUPREAGG_STAR_REL_FACTS(r)														\
+template <> struct gpupreagg_star_rel<r> {												\
+	typedef gpupreagg_star_key<GPUPREAGG_STAR_KEYLEN_##r>::type key_t;					\
+	static constexpr cl_uint	reclen = GPUPREAGG_STAR_RECLEN_##r;						\
+	static constexpr bool		narrow = (GPUPREAGG_STAR_NARROW_##r != 0);				\
+	static constexpr cl_ulong	inner_mask = GPUPREAGG_STAR_INNER_MASK_##r;				\
+	static constexpr int		nwords = (narrow ? 1 : reclen == 16 ? 4 : 2);			\
+	static_assert(GPUPREAGG_STAR_KEYLEN_##r == 4 || GPUPREAGG_STAR_KEYLEN_##r == 8, "star key width");	\
+	static_assert(narrow ? (reclen == 2 || reclen == 4) : (reclen == 8 || reclen == 16),	\
+				  "star slot record: 2 / 4 bytes narrow, 8 or 16 bytes");					\
+};
+GPUPREAGG_STAR_REL_LIST(GPUPREAGG_STAR_REL_FACTS)
+#undef GPUPREAGG_STAR_REL_FACTS
+#define GPUPREAGG_STAR_ADD_RECLEN(r)	+ gpupreagg_star_rel<r>::reclen
+static_assert(GPUPREAGG_STAR_NRELS == 1 ||
+			  (0 GPUPREAGG_STAR_REL_LIST(GPUPREAGG_STAR_ADD_RECLEN)) <= GPUPREAGG_STAR_MAXRECBYTES,
+			  "star slot records of a row");
+#define GPUPREAGG_STAR_OR_MASK(r)		| gpupreagg_star_rel<r>::inner_mask
+#define GPUPREAGG_STAR_INNER_ALL		(0UL GPUPREAGG_STAR_REL_LIST(GPUPREAGG_STAR_OR_MASK))
+template <typename T> struct gpupreagg_star_unref { typedef T type; };
+template <typename T> struct gpupreagg_star_unref<T &> { typedef T type; };
+
+/* relation R's part of a tile: where its key column and its records are, the tile's key quads,
+ * and per row ONE set of words -- w[..][0] is the row's slot until the probe replaces it by
+ * the record */
+template <int R> struct gpupreagg_star_probe {
+	typedef gpupreagg_star_rel<R>	rel;
+	typedef typename rel::key_t		key_t;
+	const char	   *keyvals;
+	const cl_uint  *keynulls;
+	const char	   *recs;
+	cl_long			key_min;
+	cl_uint			nslots;
+	key_t			keyq[GPUPREAGG_QUADS][4];
+	cl_uint			keynn[GPUPREAGG_QUADS];
+	cl_uint			w[GPUPREAGG_QUADS][4][rel::nwords];
+};
+
+#define STAR_GLOBAL(T, p)		(*(const __attribute__((address_space(1))) T *)(p))
+
+template <bool PACKED>
+__device__ __forceinline__ void
+gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
+						   const kern_data_store *kds,
+						   const gpupreagg_star_map *smap,
+						   const gpupreagg_dense_ctl *ctl,
+						   const gpupreagg_pack_ctl *pack_in_memory,
+						   char *slabs, char *lds)
+{
+	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
+	const kern_coldir *coldir = KERN_DATA_STORE_COLDIR(kds);
+	cl_uint		nitems = strom_uniform((cl_uint)kds->nitems);
+	cl_uint		ntiles = (nitems + GPUPREAGG_TILE_ROWS - 1) / GPUPREAGG_TILE_ROWS;
+	cl_uint		nsplits = ctl->nsplits;
+	cl_uint		G = ctl->groups_per_split;
+	cl_uint		NREP = ctl->nrep;
+	cl_uint		split = blockIdx.x % nsplits;
+	cl_uint		wg_in_split = blockIdx.x / nsplits;
+	cl_uint		wgs_per_split = gridDim.x / nsplits;
+	cl_uint		gid_lo = split * G;
+	cl_uint		rep = threadIdx.x & (NREP - 1);
+	cl_int		chunk_status = StromError_Success;
+	cl_ulong	summag = 0;			/* OR of the integer sums' input magnitudes */
+	cl_int		param_error = StromError_Success;
+	strom_kparams KP;
+	gpupreagg_lds_layout L;
+
+	gpupreagg_load_kparams(KP, kparams, &param_error);
+#if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
+	gpupreagg_pack_ctl pack_by_value;
+	const gpupreagg_pack_ctl *pk = &pack_by_value;
+	if (PACKED)
+	{
+		pack_by_value = *pack_in_memory;
+		cl_uint	total = pk->nwords * gpupreagg_align16(8u * G);
+		for (cl_uint i = threadIdx.x * 16; i < total; i += GPUPREAGG_BLOCK * 16)
+			*(uint4 *)(lds + i) = make_uint4(0, 0, 0, 0);
+		__syncthreads();
+	}
+	else
+#endif
+	{
+		gpupreagg_remap_init(ctl);
+		gpupreagg_lds_layout_init(L, G, NREP);
+		gpupreagg_lds_init(lds, L, G, NREP);
+	}
+	/* the virtual columns: an outer one streams from the chunk, an inner one is unpacked from
+	 * its relation's record (where in the record: uniform words of the map) */
+#define X(attno,colidx,NAME)													\
+	const bool	inner_##attno = (((GPUPREAGG_STAR_INNER_ALL >> (colidx)) & 1UL) != 0);	\
+	const cl_uint recoff_##attno = strom_uniform((cl_uint)smap->c[colidx].recoff);		\
+	const cl_uint recbit_##attno = strom_uniform((cl_uint)smap->c[colidx].nullbit);	\
+	const cl_uint nshift_##attno = strom_uniform((cl_uint)smap->c[colidx].nshift);		\
+	const cl_uint nmask_##attno = strom_uniform((cl_uint)smap->c[colidx].nmask);		\
+	const cl_long nmin_##attno = strom_uniform((cl_long)smap->c[colidx].nmin);			\
+	const char *val_##attno = (inner_##attno ? (const char *)NULL						\
+							   : (const char *)kds + coldir[smap->c[colidx].col].values_off);	\
+	const char *nul_##attno = (inner_##attno ? (const char *)NULL						\
+							   : (coldir[smap->c[colidx].col].nulls_off != 0			\
+								  ? (const char *)kds + coldir[smap->c[colidx].col].nulls_off : (const char *)NULL));
+	STROM_KVAR_LIST(X)
+#undef X
+	bool		any_nulls = false;		/* wave-uniform: picks the bitmap-free loader */
+#define X(attno,colidx,NAME)	any_nulls = any_nulls || (nul_##attno != NULL);
+	STROM_KVAR_LIST(X)
+#undef X
+#define M(r)																	\
+	gpupreagg_star_probe<r> P##r;												\
+	P##r.keyvals = (const char *)kds + coldir[smap->rel[r - 1].key_col].values_off;	\
+	P##r.keynulls = (coldir[smap->rel[r - 1].key_col].nulls_off != 0			\
+					 ? (const cl_uint *)((const char *)kds + coldir[smap->rel[r - 1].key_col].nulls_off)	\
+					 : (const cl_uint *)NULL);									\
+	P##r.recs = (const char *)smap->rel[r - 1].recs;							\
+	P##r.key_min = smap->rel[r - 1].key_min;									\
+	P##r.nslots = smap->rel[r - 1].nslots;										\
+	any_nulls = any_nulls || (P##r.keynulls != NULL);
+	GPUPREAGG_STAR_REL_LIST(M)
+#undef M
+	/* a qual that reads outer columns only is evaluated BEFORE any probe (see
+	 * gpupreagg_dense_lookup_body); gpupreagg_dense_row evaluates it again, errors included, for
+	 * the rows that have a partner in every relation */
+	const bool	qual_first = ((GPUPREAGG_QUAL_VARMASK & GPUPREAGG_STAR_INNER_ALL) == 0 && GPUPREAGG_QUAL_VARMASK != 0);
+	/* (an inner column may be NULL whatever the chunk's bitmaps say) */
+	const cl_uint rowflags = ((any_nulls || GPUPREAGG_STAR_INNER_ALL != 0) ? 0u : ROWFLAG_ALL_NOTNULL);
+
+	char	   *my_slab = slabs + (size_t)blockIdx.x * ctl->slab_bytes;
+#if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
+	if (PACKED && pk->spill_at != 0)
+	{
+		gpupreagg_packed_slab_zero(pk, my_slab, G);
+		__syncthreads();
+	}
+#endif
+	/* relation P's key quads of quad k */
+	auto load_keys = [&](auto &P, int k, cl_uint row0, bool full_tile)
+	{
+		typedef typename gpupreagg_star_unref<decltype(P)>::type::key_t key_t;
+		if (full_tile && !any_nulls)
+			strom_column_load_quad<key_t, true, true>(P.keyvals, P.keynulls, row0, nitems, P.keyq[k], P.keynn[k]);
+		else if (full_tile)
+			strom_column_load_quad<key_t, true>(P.keyvals, P.keynulls, row0, nitems, P.keyq[k], P.keynn[k]);
+		else
+			strom_column_load_quad<key_t, false>(P.keyvals, P.keynulls, row0, nitems, P.keyq[k], P.keynn[k]);
+	};
+	/* the key of row (k, j) becomes its slot; false: NULL or outside the table */
+	auto key_to_slot = [&](auto &P, int k, int j) -> bool
+	{
+		cl_ulong	s64 = (cl_ulong)((cl_long)P.keyq[k][j] - P.key_min);
+		P.w[k][j][0] = (cl_uint)s64;
+		return ((P.keynn[k] >> j) & 1) && s64 < P.nslots;
+	};
+	/* the probes of relation P: one load per row, dead rows at slot 0 */
+	auto probe = [&](auto &P, const cl_uint (&gone)[GPUPREAGG_QUADS])
+	{
+		typedef typename gpupreagg_star_unref<decltype(P)>::type::rel rel;
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				cl_uint		slot = (((gone[k] >> j) & 1) ? 0u : P.w[k][j][0]);
+				const char *rec = P.recs + (size_t)rel::reclen * slot;
+				if (rel::narrow)
+					P.w[k][j][0] = (rel::reclen == 2 ? (cl_uint)STAR_GLOBAL(cl_ushort, rec) : STAR_GLOBAL(cl_uint, rec));
+				else if (rel::reclen == 8)
+				{
+					cl_ulong q = STAR_GLOBAL(cl_ulong, rec);
+					P.w[k][j][0] = (cl_uint)q;
+					P.w[k][j][rel::nwords > 1 ? 1 : 0] = (cl_uint)(q >> 32);
+				}
+				else
+				{
+					/* (a clang vector, not HIP's uint4 struct: that one is copied through a generic
+					 * reference, and the load becomes a flat_load) */
+					strom_quad<cl_uint>::vec_t q = STAR_GLOBAL(strom_quad<cl_uint>::vec_t, rec);
+					P.w[k][j][0] = q.x;
+					P.w[k][j][rel::nwords > 1 ? 1 : 0] = q.y;
+					P.w[k][j][rel::nwords > 2 ? 2 : 0] = q.z;
+					P.w[k][j][rel::nwords > 3 ? 3 : 0] = q.w;
+				}
+			}
+		}
+	};
+
+	for (cl_uint tile = wg_in_split; tile < ntiles; tile += wgs_per_split)
+	{
+		cl_uint		tile_base = tile * GPUPREAGG_TILE_ROWS;
+		bool		full_tile = (tile_base + GPUPREAGG_TILE_ROWS <= nitems);
+		gpupreagg_column_tile T;
+		cl_uint		gone[GPUPREAGG_QUADS];			/* bit j: no partner in some relation */
+		cl_uint		qual_ok[GPUPREAGG_QUADS];		/* bit j: the qual was seen to pass, without an error */
+
+		/* the tile's streamed columns: every relation's key column and the outer columns */
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+			cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
+#define M(r)	load_keys(P##r, k, row0, full_tile);
+			GPUPREAGG_STAR_REL_LIST(M)
+#undef M
+			if (full_tile && !any_nulls)
+			{
+#define X(attno,colidx,NAME)													\
+				if (!inner_##attno)												\
+					strom_column_load_quad<pg_##NAME##_base_t, true, true>(val_##attno, (const cl_uint *)nul_##attno,	\
+															   row0, nitems, T.v_##attno[k], T.nn_##attno[k]);
+				STROM_KVAR_LIST(X)
+#undef X
+			}
+			else if (full_tile)
+			{
+#define X(attno,colidx,NAME)													\
+				if (!inner_##attno)												\
+					strom_column_load_quad<pg_##NAME##_base_t, true>(val_##attno, (const cl_uint *)nul_##attno,	\
+															   row0, nitems, T.v_##attno[k], T.nn_##attno[k]);
+				STROM_KVAR_LIST(X)
+#undef X
+			}
+			else
+			{
+#define X(attno,colidx,NAME)													\
+				if (!inner_##attno)												\
+					strom_column_load_quad<pg_##NAME##_base_t, false>(val_##attno, (const cl_uint *)nul_##attno,	\
+															   row0, nitems, T.v_##attno[k], T.nn_##attno[k]);
+				STROM_KVAR_LIST(X)
+#undef X
+			}
+		}
+		/* keys -> slots; a row is dead here when a key is NULL or outside its table, or the
+		 * qual-first rejects it (without an error) */
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+			cl_uint	row0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
+			gone[k] = 0;
+			qual_ok[k] = 0;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				bool		live = (full_tile || row0 + j < nitems);
+#define M(r)	live = key_to_slot(P##r, k, j) && live;
+				GPUPREAGG_STAR_REL_LIST(M)
+#undef M
+				if (qual_first && live)
+				{
+					strom_kvars	KV;
+					cl_int		qerr = param_error;
+#define X(attno,colidx,NAME)													\
+					KV.KVAR_##attno = (inner_##attno								\
+						? pg_##NAME##_make((pg_##NAME##_base_t)0, true)			\
+						: pg_##NAME##_make(T.v_##attno[k][j], !((T.nn_##attno[k] >> j) & 1)));
+					STROM_KVAR_LIST(X)
+#undef X
+					STROM_KVARS_FINISH(KV);
+					pg_bool_t	rc = gpupreagg_qual_eval(&qerr, KP, KV);
+					live = !(qerr == StromError_Success && !EVAL(rc));
+					qual_ok[k] |= ((qerr == StromError_Success && EVAL(rc)) ? (1u << j) : 0u);
+				}
+				gone[k] |= (live ? 0u : (1u << j));
+			}
+		}
+		/* every probe of the tile, all relations, before the first record is used */
+#define M(r)	probe(P##r, gone);
+		GPUPREAGG_STAR_REL_LIST(M)
+#undef M
+		/* relation after relation: presence into 'gone', its inner columns into T */
+#define X(attno,colidx,NAME)													\
+		if (((rel::inner_mask >> (colidx)) & 1UL) != 0)								\
+		{																		\
+			cl_uint nn = 0;														\
+			_Pragma("unroll")													\
+			for (int j = 0; j < 4; j++)											\
+			{																	\
+				pg_##NAME##_base_t val;											\
+				cl_uint	flags = P.w[k][j][0];									\
+				if (rel::narrow)												\
+					val = (pg_##NAME##_base_t)(nmin_##attno +					\
+						(cl_long)((flags >> nshift_##attno) & nmask_##attno));	\
+				else															\
+				{																\
+					/* (offsets are uniform: the selects are scalar) */			\
+					cl_uint	wi = recoff_##attno >> 2;							\
+					cl_uint	w1 = P.w[k][j][rel::nwords > 1 ? 1 : 0];			\
+					cl_uint	w2 = (rel::nwords > 2 ? P.w[k][j][rel::nwords > 2 ? 2 : 0] : 0u);	\
+					cl_uint	w3 = (rel::nwords > 3 ? P.w[k][j][rel::nwords > 3 ? 3 : 0] : 0u);	\
+					cl_uint	lo = (wi == 1 ? w1 : wi == 2 ? w2 : w3);			\
+					cl_uint	hi = (wi == 2 ? w3 : 0u);							\
+					cl_ulong bits = (((cl_ulong)hi << 32) | lo) >> ((recoff_##attno & 3u) * 8u);	\
+					__builtin_memcpy(&val, &bits, sizeof(val));					\
+				}																\
+				T.v_##attno[k][j] = val;										\
+				nn |= (((flags >> recbit_##attno) & 1u) ? 0u : (1u << j));		\
+			}																	\
+			T.nn_##attno[k] = nn;												\
+		}
+		auto decode = [&](auto &P)
+		{
+			typedef typename gpupreagg_star_unref<decltype(P)>::type::rel rel;
+#pragma unroll
+			for (int k = 0; k < GPUPREAGG_QUADS; k++)
+			{
+				cl_uint	ab = 0;
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+					ab |= ((P.w[k][j][0] & 1u) ? 0u : (1u << j));
+				gone[k] |= ab;
+				STROM_KVAR_LIST(X)
+			}
+		};
+#undef X
+#define M(r)	decode(P##r);
+		GPUPREAGG_STAR_REL_LIST(M)
+#undef M
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				if (!((gone[k] >> j) & 1))
+				{
+					strom_kvars	KV;
+					gpupreagg_tile_row(KV, T, k, j);
+					STROM_KVARS_FINISH(KV);
+#if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
+					if (PACKED)
+						gpupreagg_packed_row(lds, ctl, pk, KP, KV, gid_lo, G, param_error, &chunk_status, my_slab,
+											 (qual_ok[k] >> j) & 1);
+					else
+#endif
+						gpupreagg_dense_row(lds, ctl, L, KP, KV, gid_lo, G, NREP, rep,
+											param_error, &chunk_status, summag, rowflags, (qual_ok[k] >> j) & 1);
+				}
+			}
+		}
+	}
+#if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
+	if (PACKED)
+		gpupreagg_store_slab_packed(lds, pk, my_slab, G, pk->spill_at != 0);
+	else
+#endif
+		gpupreagg_store_slab(lds, L, my_slab, G, NREP, &chunk_status, rowflags);
+	gpupreagg_writeback_status(&kgpreagg->status, chunk_status);
+	gpupreagg_writeback_summag(kgpreagg, summag);
+}
+
+extern "C" __global__ void
+__launch_bounds__(GPUPREAGG_BLOCK)
+gpupreagg_dense_lookup_star(kern_gpupreagg *kgpreagg,
+							const kern_data_store *kds,
+							const gpupreagg_star_map *smap,
+							const gpupreagg_dense_ctl *ctl_in_memory,
+							char *slabs)
+{
+	extern __shared__ __attribute__((aligned(16))) char lds[];
+	/* the control block by value (see gpupreagg_dense_column) */
+	const gpupreagg_dense_ctl ctl_by_value = *ctl_in_memory;
+	const gpupreagg_dense_ctl *ctl = &ctl_by_value;
+	gpupreagg_star_lookup_body<false>(kgpreagg, kds, smap, ctl, NULL, slabs, lds);
+}
+
+#if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
+/* the same with packed accumulators: the summed columns are OUTER columns without NULLs */
+extern "C" __global__ void
+__launch_bounds__(GPUPREAGG_BLOCK)
+gpupreagg_packed_lookup_star(kern_gpupreagg *kgpreagg,
+							 const kern_data_store *kds,
+							 const gpupreagg_star_map *smap,
+							 const gpupreagg_dense_ctl *ctl_in_memory,
+							 const gpupreagg_pack_ctl *pack_in_memory,
+							 char *slabs)
+{
+	extern __shared__ __attribute__((aligned(16))) char lds[];
+	const gpupreagg_dense_ctl ctl_by_value = *ctl_in_memory;
+	const gpupreagg_dense_ctl *ctl = &ctl_by_value;
+	gpupreagg_star_lookup_body<true>(kgpreagg, kds, smap, ctl, pack_in_memory, slabs, lds);
+}
+#endif
+#undef STAR_GLOBAL
+#endif	/* GPUPREAGG_STAR_NRELS */
+
+/* ====================================================================== *
  * register accumulators: at most GPUPREAGG_REG_GROUPS dense ids
  *
  * LDS atomics cost ~24 (u32) / ~53 (u64) / ~110 (f64) cycles per wave

@@ -511,7 +511,9 @@ struct preagg_request {
 	void			   *joined_buffer = nullptr;	/* the join's device image, owned by this request now */
 	bool				lookup = false;				/* no result pairs: the join is a lookup in the aggregate's pass */
 	Program			   *prog = nullptr;				/* lookup: the session's program built for this column mapping */
-	std::shared_ptr<std::vector<char>> joined_map;	/* a gpupreagg_joined_map */
+	std::shared_ptr<std::vector<char>> joined_map;	/* a gpupreagg_joined_map; star: a gpupreagg_star_map */
+	bool				star = false;				/* lookup over a star of relations (gpupreagg_dense_lookup_star) */
+	std::string			star_defs;					/* ... the define block 'prog' was built with */
 	/* hashed, exact fold (gpupreagg_hashed_exact): 'sess' is a scratch session of this one */
 	strom_gpupreagg	   *exact_parent = nullptr;
 };
@@ -637,6 +639,61 @@ lookup_mapping_program(strom_gpupreagg *sess, const gpupreagg_joined_map *jm)
 	return prog;
 }
 
+/* the define block of a star mapping (strom_gpupreagg.h: GPUPREAGG_STAR_*); "" = no valid mapping */
+std::string
+star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, const int32_t *narrow,
+					 const uint64_t *inner_mask)
+{
+	if (nrels < 1 || nrels > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask)
+		return "";
+	char		buf[256];
+	snprintf(buf, sizeof(buf), "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_STAR_NRELS %d\n", nrels);
+	std::string	defs = buf;
+	unsigned	total = 0;
+	for (int r = 0; r < nrels; r++)
+	{
+		bool	ok = (narrow[r] ? (reclen[r] == 2 || reclen[r] == 4) : (reclen[r] == 8 || reclen[r] == 16));
+		if (!ok || !(keylen[r] == 4 || keylen[r] == 8))
+			return "";
+		for (int q = 0; q < r; q++)
+			if (inner_mask[q] & inner_mask[r])
+				return "";					/* a column has one source */
+		total += (unsigned)reclen[r];
+		snprintf(buf, sizeof(buf),
+				 "#define GPUPREAGG_STAR_RECLEN_%d %d\n#define GPUPREAGG_STAR_NARROW_%d %d\n"
+				 "#define GPUPREAGG_STAR_KEYLEN_%d %d\n#define GPUPREAGG_STAR_INNER_MASK_%d 0x%lxUL\n",
+				 r + 1, reclen[r], r + 1, narrow[r] ? 1 : 0, r + 1, keylen[r], r + 1, (unsigned long)inner_mask[r]);
+		defs += buf;
+	}
+	if (total > GPUPREAGG_STAR_MAXRECBYTES)
+		return "";
+	return defs;
+}
+
+/*
+ * star of lookups: the session's source built FOR the mapping, like lookup_mapping_program -- and
+ * ALWAYS: the star kernels have no run-time-mapping form (STROM_GPUPREAGG_LOOKUP_GENERIC is the
+ * one-table call's).  checked: the same with GPUPREAGG_CHECKED, for a chunk whose integer sums
+ * the range proof did not cover (ensure_checked_program is the session's own source, which has
+ * no star kernel).
+ */
+Program *
+star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs, bool checked = false)
+{
+	std::string	defs = (checked ? "#define GPUPREAGG_CHECKED 1\n" : "") + star_defs;
+	std::lock_guard<std::mutex> g(sess->lock);
+	auto	it = sess->lookup_programs.find(defs);
+	if (it != sess->lookup_programs.end())
+		return it->second.second;
+	std::string	source = defs + sess->prog->source;
+	strom_devprog_key key = strom_get_devprog_key(source.c_str(), sess->prog->extra_flags);
+	Program	   *prog = (key ? lookup_program(key) : nullptr);
+	if (!prog)
+		return nullptr;
+	sess->lookup_programs[defs] = std::make_pair(key, prog);
+	return prog;
+}
+
 /*
  * the program that folds a chunk whose integer sums could not be proven to stay in
  * int8 (strom_gpupreagg.h, "integer sums never wrap"): the session's own source built with
@@ -663,7 +720,8 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 {
 	strom_gpupreagg *sess = req.sess;
 	Device	   *dev = task->dev;
-	Program	   *prog = (checked ? sess->prog_checked : req.prog ? req.prog : sess->prog);
+	/* (a star request brings its program either way: star_mapping_program) */
+	Program	   *prog = ((checked && !req.star) ? sess->prog_checked : req.prog ? req.prog : sess->prog);
 	int			errcode = 0;
 
 	(void)hipSetDevice(dev->hip_id);
@@ -697,7 +755,8 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 						  req.krowmap == nullptr && req.rowmap_dev == nullptr);
 	/* (the checked program adds in LDS with returning atomics: the LDS-atomics kernels only) */
 	bool	use_reg = (use_column && sess->reg_groups != 0 && !checked);
-	hipFunction_t fn = prog->get_function(dev, use_lookup ? "gpupreagg_dense_lookup"
+	hipFunction_t fn = prog->get_function(dev, req.star ? "gpupreagg_dense_lookup_star"
+										  : use_lookup ? "gpupreagg_dense_lookup"
 										  : use_joined ? "gpupreagg_dense_joined"
 										  : use_reg ? (sess->reg_groups == 1 ? "gpupreagg_reg1_column"
 																			  : "gpupreagg_priv_column")
@@ -717,7 +776,8 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 	if ((use_lookup || (use_column && !use_reg)) && sess->packable && sess->ctl.nsplits > 1 && !checked)
 	{
 		int		e2 = 0;
-		hipFunction_t fn_packed = prog->get_function(dev, use_lookup ? "gpupreagg_packed_lookup"
+		hipFunction_t fn_packed = prog->get_function(dev, req.star ? "gpupreagg_packed_lookup_star"
+													 : use_lookup ? "gpupreagg_packed_lookup"
 													 : "gpupreagg_packed_column", &e2);
 		std::shared_ptr<std::vector<kern_coldir>> snap;
 		std::vector<kern_coldir> virt;
@@ -738,17 +798,21 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 			/* the program's columns are virtual: an outer column brings its own
 			 * directory entry, an inner column counts as "may be NULL, no zone map" */
 			const gpupreagg_joined_map *jm = (const gpupreagg_joined_map *)req.joined_map->data();
-			virt.resize(jm->ncols);
-			for (cl_uint i = 0; i < jm->ncols; i++)
+			const gpupreagg_star_map *sm = (const gpupreagg_star_map *)req.joined_map->data();
+			cl_uint		nvirt = (req.star ? sm->ncols : jm->ncols);
+			virt.resize(nvirt);
+			for (cl_uint i = 0; i < nvirt; i++)
 			{
+				cl_int		depth = (req.star ? sm->c[i].depth : jm->c[i].depth);
+				cl_int		col = (req.star ? sm->c[i].col : jm->c[i].col);
 				memset(&virt[i], 0, sizeof(kern_coldir));
-				if (jm->c[i].depth == 0 && jm->c[i].col >= 0 && (cl_uint)jm->c[i].col < ncols)
-					virt[i] = coldir[jm->c[i].col];
+				if (depth == 0 && col >= 0 && (cl_uint)col < ncols)
+					virt[i] = coldir[col];
 				else
 					virt[i].nulls_off = 1;
 			}
 			coldir = virt.data();
-			ncols = jm->ncols;
+			ncols = nvirt;
 		}
 		packed = packed_plan(sess, fn_packed, coldir, ncols, req.nrows, &pk);
 		if (packed)
@@ -1053,6 +1117,19 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 			 */
 			t->retry = [t, req]()
 			{
+				if (req.star)
+				{
+					/* the star kernels live in the mapping's own program: its checked build */
+					preagg_request again = req;
+					again.prog = star_mapping_program(req.sess, req.star_defs, true);
+					if (!again.prog)
+					{
+						task_fail(t, StromError_OutOfMemory);
+						return;
+					}
+					program_run_or_park(again.prog, [t, again]() { gpupreagg_launch(t, again, true); });
+					return;
+				}
 				int		rc = ensure_checked_program(req.sess);
 				if (rc != 0)
 				{
@@ -2501,6 +2578,186 @@ strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
 {
 	return submit_gpupreagg_over_join(sess, nullptr, true, tbl, outer, ncols, src_depth, src_colidx,
 									  type_oids, done, arg, p_errcode);
+}
+
+extern "C" int
+strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+									const int32_t *narrow, const uint64_t *inner_mask,
+									char *buf, size_t buflen)
+{
+	std::string	defs = star_mapping_defines(ntbls, keylen, reclen, narrow, inner_mask);
+	if (defs.empty() || !buf || defs.size() + 1 > buflen)
+		return -1;
+	memcpy(buf, defs.c_str(), defs.size() + 1);
+	return (int)defs.size();
+}
+
+/*
+ * a star of lookups inside the aggregate's own pass (gpupreagg_dense_lookup_star): see strom_hip.h.
+ * One table per relation: hashjoin_table_direct_info / hashjoin_table_dimrecs (the narrow records
+ * and the per-table cache included) serve each relation as they serve the one-table call.
+ */
+extern "C" strom_task *
+strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
+								   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
+								   int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+								   const int32_t *type_oids,
+								   strom_done_cb done, void *arg, int *p_errcode)
+{
+	static_assert(STROM_LOOKUP_STAR_MAXRELS == GPUPREAGG_STAR_MAXRELS, "star relations");
+	if (ntbls == 1 && tbls)
+		return submit_gpupreagg_over_join(sess, nullptr, true, tbls[0], outer, ncols, src_depth, src_colidx,
+										  type_oids, done, arg, p_errcode);
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = StromError_BadRequestMessage;
+	if (!sess || sess->hashed || !sess->has_domain || !tbls || !outer ||
+		ntbls < 1 || ntbls > STROM_LOOKUP_STAR_MAXRELS ||
+		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids ||
+		outer->head.format != KDS_FORMAT_COLUMN ||
+		/* (these kernels stream the outer columns; text variables take the plain fold) */
+		(sess->prog->extra_flags & DEVTYPE_IS_VARLENA) != 0 ||
+		outer->dindex != sess->dev->dindex)
+		return nullptr;
+	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_star_map), 0);
+	gpupreagg_star_map *sm = (gpupreagg_star_map *)img->data();
+	int		key_attno[STROM_LOOKUP_STAR_MAXRELS];
+	int		outer_ncols = (int)outer->head.ncols;
+
+	sm->ncols = ncols;
+	sm->nrels = ntbls;
+	for (int r = 0; r < ntbls; r++)
+	{
+		int		tbl_dindex = -1, has_outer_qual = 0;
+		if (!tbls[r] ||
+			hashjoin_table_direct_info(tbls[r], &sm->rel[r].key_min, &sm->rel[r].nslots, &key_attno[r],
+									   &tbl_dindex, &has_outer_qual) != 0 ||
+			/* only the aggregate program runs: a WHERE in a join program would not be applied */
+			has_outer_qual || key_attno[r] < 1 || key_attno[r] > outer_ncols ||
+			tbl_dindex != sess->dev->dindex)
+			return nullptr;
+		sm->rel[r].key_col = key_attno[r] - 1;
+	}
+	for (int i = 0; i < ncols; i++)
+		if (src_depth[i] < 0 || src_depth[i] > ntbls || src_colidx[i] < 0)
+			return nullptr;
+	(void)hipSetDevice(sess->dev->hip_id);
+	/* the outer chunk's column widths */
+	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
+	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
+		return nullptr;
+	const kern_data_store *oh = (const kern_data_store *)ohead.data();
+	auto attlen_of = [](int32_t type_oid) -> int {
+		switch (type_oid < 0 ? -type_oid : type_oid)
+		{
+			case STROM_BOOLOID: case STROM_BPCHAROID:	return 1;
+			case STROM_INT2OID:							return 2;
+			case STROM_INT4OID: case STROM_FLOAT4OID: case STROM_DATEOID:	return 4;
+			default:									return 8;
+		}
+	};
+	for (int r = 0; r < ntbls; r++)
+	{
+		sm->rel[r].key_attlen = oh->colmeta[key_attno[r] - 1].attlen;
+		if (!(sm->rel[r].key_attlen == 4 || sm->rel[r].key_attlen == 8))
+			return nullptr;
+	}
+	for (int i = 0; i < ncols; i++)
+	{
+		sm->c[i].depth = src_depth[i];
+		sm->c[i].col = src_colidx[i];
+		if (src_depth[i] == 0 &&
+			(src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen_of(type_oids[i])))
+		{
+			*p_errcode = StromError_DataStoreCorruption;
+			return nullptr;
+		}
+	}
+	int32_t		keylen[STROM_LOOKUP_STAR_MAXRELS], reclens[STROM_LOOKUP_STAR_MAXRELS], narrows[STROM_LOOKUP_STAR_MAXRELS];
+	uint64_t	masks[STROM_LOOKUP_STAR_MAXRELS];
+	for (int r = 0; r < ntbls; r++)
+	{
+		/* one packed record per slot: presence, NULL bits and the wanted columns of relation r + 1 */
+		const int MAXCOLS = HASHJOIN_DIMREC_MAXCOLS;
+		int		cols[MAXCOLS], lens[MAXCOLS], which[MAXCOLS], ints[MAXCOLS], n = 0;
+		unsigned offs[MAXCOLS], reclen = 0;
+		void   *recs = nullptr;
+		dimrec_narrow nw;
+
+		masks[r] = 0;
+		for (int i = 0; i < ncols; i++)
+		{
+			if (src_depth[i] != r + 1)
+				continue;
+			if (n == MAXCOLS)
+				return nullptr;
+			int		oid = (type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
+			cols[n] = src_colidx[i];
+			lens[n] = attlen_of(type_oids[i]);
+			ints[n] = !(oid == STROM_FLOAT4OID || oid == STROM_FLOAT8OID || oid == STROM_NUMERICOID);
+			which[n++] = i;
+			masks[r] |= ((uint64_t)1 << i);
+		}
+		int		rc = hashjoin_table_dimrecs(tbls[r], n, cols, lens, offs, &recs, &reclen, ints, &nw);
+		if (rc != 0)
+		{
+			*p_errcode = rc;
+			return nullptr;
+		}
+		for (int k = 0; k < n; k++)
+		{
+			sm->c[which[k]].recoff = offs[k];
+			sm->c[which[k]].nullbit = 1 + k;
+		}
+		sm->rel[r].recs = (cl_ulong)(uintptr_t)recs;
+		sm->rel[r].reclen = reclen;
+		if (nw.spec.reclen != 0)
+		{
+			sm->rel[r].recs = (cl_ulong)(uintptr_t)nw.recs;
+			sm->rel[r].reclen = nw.spec.reclen;
+			sm->rel[r].narrow = 1;
+			for (int k = 0; k < n; k++)
+			{
+				sm->c[which[k]].recoff = 0;
+				sm->c[which[k]].nshift = nw.spec.shift[k];
+				sm->c[which[k]].nmask = nw.spec.mask[k];
+				sm->c[which[k]].nmin = nw.spec.vmin[k];
+			}
+		}
+		keylen[r] = sm->rel[r].key_attlen;
+		reclens[r] = (int32_t)sm->rel[r].reclen;
+		narrows[r] = (int32_t)sm->rel[r].narrow;
+	}
+	/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
+	 * all relations: no define block -- the kernel keeps a row's records in registers) */
+	preagg_request req;
+	req.star_defs = star_mapping_defines(ntbls, keylen, reclens, narrows, masks);
+	if (req.star_defs.empty())
+		return nullptr;
+	req.prog = star_mapping_program(sess, req.star_defs);
+	if (!req.prog)
+	{
+		*p_errcode = StromError_OutOfMemory;
+		return nullptr;
+	}
+	req.sess = sess;
+	req.kds = nullptr;
+	req.kds_dev = outer;
+	req.krowmap = nullptr;
+	req.rowmap_dev = nullptr;
+	req.format = KDS_FORMAT_COLUMN;
+	req.joined_map = img;
+	req.lookup = true;
+	req.star = true;
+	req.nrows = outer->head.nitems;
+	*p_errcode = 0;
+	sess->nfolds++;
+	strom_task_impl *task = task_create(sess->dev, done, arg);
+	program_run_or_park(req.prog, [task, req]() { gpupreagg_launch(task, req); });
+	return task;
+	STROM_ABI_CATCH(nullptr, p_errcode)
 }
 
 /*

@@ -71,6 +71,24 @@ def domain_of(chunks, key_columns):
     return dom
 
 
+def lookup_star_defines(relations):
+    """the define block the runtime puts in front of a session's source to build the star kernels
+    (gpupreagg_dense_lookup_star / gpupreagg_packed_lookup_star) for a mapping; no device needed.
+    relations: per relation (key length 4 or 8, slot record length, narrow?, [0-based virtual
+    columns it serves]).  The program text is lookup_star_defines(...) + codegen.source."""
+    n = len(relations)
+    keylen = np.array([r[0] for r in relations], dtype=np.int32)
+    reclen = np.array([r[1] for r in relations], dtype=np.int32)
+    narrow = np.array([1 if r[2] else 0 for r in relations], dtype=np.int32)
+    masks = np.array([sum(1 << c for c in r[3]) for r in relations], dtype=np.uint64)
+    buf = ctypes.create_string_buffer(4096)
+    rc = lib.strom_gpupreagg_lookup_star_defines(n, keylen.ctypes.data, reclen.ctypes.data,
+                                                 narrow.ctypes.data, masks.ctypes.data, buf, len(buf))
+    if rc < 0:
+        raise ValueError("no star mapping: %r" % (relations,))
+    return buf.value.decode()
+
+
 class PartialRows(object):
     """decoded TUPSLOT result: one partial row per group"""
 
@@ -237,6 +255,24 @@ class GpuPreAgg(object):
         if not task:
             raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup")
         return (task, chunk, (depth, colidx, oids))
+
+    def submit_lookup_star(self, joins, chunk, columns):
+        """fact JOIN dim1 JOIN dim2 ... GROUP BY in one pass (strom_submit_gpupreagg_lookup_star):
+        joins[d - 1] lends relation d's hash table (its program names the outer column that joins
+        it); columns as in join_to_column with depth 0 .. len(joins).  An inner join: a row is
+        folded only if every relation has a partner."""
+        from .kds import SQL_TYPES
+        depth = np.array([d for d, _, _ in columns], dtype=np.int32)
+        colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
+        oids = np.array([SQL_TYPES[t][0] for _, _, t in columns], dtype=np.int32)
+        tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpupreagg_lookup_star(self.session, tbls, len(joins), chunk.handle,
+                                                      len(columns), depth.ctypes.data, colidx.ctypes.data,
+                                                      oids.ctypes.data, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_star")
+        return (task, chunk, (depth, colidx, oids, tbls))
 
     def collect(self, pending):
         """returns (status, perfmon): status 0 folded, 2 CpuReCheck (not folded)"""

@@ -500,6 +500,15 @@ strom_dstore *strom_hashjoin_project_column(strom_task *join_task, strom_hashjoi
  * plain outer column: inner columns then come from slot-indexed arrays the
  * table builds on first use.  Anything else answers BadRequest and the
  * caller goes through strom_hashjoin_project_column().
+ * Text / character(n): a variable of the program with one of these types
+ * must be a column of 'outer' -- src_depth 0, type_oids STROM_TEXTOID /
+ * STROM_BPCHARNOID as the variable's own type, onto a column with attlen
+ * -1; the kernel turns the column's 8-byte offsets into datum addresses
+ * (offset and datum inside the chunk, else DataStoreCorruption; a
+ * compressed or external datum in a row that is folded: CpuReCheck, the
+ * chunk is not folded).  A text variable mapped to the inner relation, onto
+ * a by-value column or under another type answers BadRequest with nothing
+ * launched: slot records hold fixed-width values only.
  */
 strom_task *strom_submit_gpupreagg_joined(strom_gpupreagg *sess, strom_task *join_task,
 										  strom_hashjoin_table *tbl, strom_dstore *outer,
@@ -519,6 +528,10 @@ strom_task *strom_submit_gpupreagg_joined(strom_gpupreagg *sess, strom_task *joi
  * (only the aggregate program runs): a table whose program carries a
  * pulled-up outer qual or a join qual is refused with BadRequest -- put the
  * WHERE into the aggregate program, or go through _joined / the plain join.
+ * Text / character(n) variables as for _joined: fact columns only (depth 0,
+ * the variable's own type, a column with attlen -1), BadRequest otherwise.
+ * A WHERE over fact columns alone, text included, runs before the probe; an
+ * unreadable or corrupt datum there counts only for a row with a partner.
  */
 strom_task *strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
 										  strom_hashjoin_table *tbl, strom_dstore *outer,
@@ -541,7 +554,9 @@ strom_task *strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
  * ntbls == 1 is strom_submit_gpupreagg_lookup.  BadRequest, and nothing is launched: ntbls
  * outside 1 .. STROM_LOOKUP_STAR_MAXRELS, a depth outside 0 .. ntbls, a table that fails the
  * requirements above or lives on another device, a hashed session, a session without a domain, a
- * program with varlena variables, a key that is not 4 or 8 bytes wide, and for ntbls >= 2 a
+ * text / character(n) variable of the program that is not mapped to depth 0, under its own type
+ * (STROM_TEXTOID / STROM_BPCHARNOID), onto an outer column with attlen -1 (no relation serves a
+ * text column: slot records hold fixed-width values), a key that is not 4 or 8 bytes wide, and for ntbls >= 2 a
  * relation whose slot record is longer than 16 bytes or records that total more than 32 bytes
  * over all relations (the kernel holds a row's records of all relations in registers): the
  * caller then goes through the plain join and strom_hashjoin_project_column().

@@ -72,9 +72,16 @@ struct strom_kvars {
 /*
  * text / character(n) variables of a row taken from COLUMN arrays: offset -> address
  * (strom_common.h).  Called by the row-at-a-time kernels and by the streaming dense kernels
- * (dense / packed / reg1 / priv _column); the hash roles' scans and the lookup / joined variants
- * do not, and the host keeps a program with such variables away from them (gpupreagg.cpp:
- * column_streams, strom_submit_gpupreagg_joined / _lookup).
+ * (dense / packed / reg1 / priv _column); the hash roles' scans do not, and the host keeps a
+ * program with such variables away from them (gpupreagg.cpp: column_streams).
+ *
+ * The fused join-and-aggregate kernels (lookup, star, joined) call strom_kvars_from_outer_column
+ * instead: their (var N ...) number the VIRTUAL joined relation, so N - 1 is no column of the
+ * chunk and kds->colmeta[N - 1] says nothing about the variable.  The host accepts such a request
+ * only when every text variable maps to depth 0, onto a chunk column with attlen == -1, under its
+ * own type (gpupreagg.cpp: varlena_mapping_ok); what is left for the device is the offset and the
+ * datum's length against kds->length and the datum's header (pg_<type>_from_offset).  An inner
+ * variable never gets here as text: slot records hold fixed-width values only.
  */
 #ifndef STROM_KVARLENA_LIST
 #define STROM_KVARLENA_LIST(X)
@@ -83,6 +90,51 @@ struct strom_kvars {
 #define GPUPREAGG_HAS_VARLENA_VARS	1
 #endif
 STROM_DEFINE_KVARS_FROM_COLUMN
+#define STROM_KVARLENA_FIX_OUTER(attno,NAME)	\
+	KV.KVAR_##attno = pg_##NAME##_from_offset(errcode, kds, KV.KVAR_##attno);
+STROM_DEVICE void
+strom_kvars_from_outer_column(strom_kvars &KV, const kern_data_store *kds, cl_int *errcode)
+{
+	STROM_KVARLENA_LIST(STROM_KVARLENA_FIX_OUTER)
+}
+/*
+ * The two call sites of the lookup and star bodies.  A program without text variables keeps its
+ * code token for token (the run-time-mapping kernels spill, and a copied error word moved their
+ * instruction count): the conversion and the row's own error word exist only with text variables.
+ * GPUPREAGG_OUTER_QUAL_VARS: in the qual-first stage, errors go to the qual's error word;
+ * GPUPREAGG_OUTER_ROW_VARS: in front of the row function, which goes on with GPUPREAGG_ROW_ERROR.
+ */
+#if GPUPREAGG_HAS_VARLENA_VARS
+#define GPUPREAGG_OUTER_QUAL_VARS(KV, qerr)	strom_kvars_from_outer_column(KV, kds, &(qerr))
+#define GPUPREAGG_OUTER_ROW_VARS(KV)			\
+	cl_int		row_error = param_error;		\
+	strom_kvars_from_outer_column(KV, kds, &row_error)
+#define GPUPREAGG_ROW_ERROR					row_error
+#else
+#define GPUPREAGG_OUTER_QUAL_VARS(KV, qerr)	((void)0)
+#define GPUPREAGG_OUTER_ROW_VARS(KV)			((void)0)
+#define GPUPREAGG_ROW_ERROR					param_error
+#endif
+/* one variable of the joined kernel's pair-at-a-time gather: a text offset becomes an address as
+ * above, anything else passes through */
+template <typename PGT>
+STROM_DEVICE PGT
+gpupreagg_outer_datum(cl_int *errcode, const kern_data_store *kds, PGT v)
+{
+	return v;
+}
+#if GPUPREAGG_HAS_VARLENA_VARS
+STROM_DEVICE pg_text_t
+gpupreagg_outer_datum(cl_int *errcode, const kern_data_store *kds, pg_text_t v)
+{
+	return pg_text_from_offset(errcode, kds, v);
+}
+STROM_DEVICE pg_bpcharn_t
+gpupreagg_outer_datum(cl_int *errcode, const kern_data_store *kds, pg_bpcharn_t v)
+{
+	return pg_bpcharn_from_offset(errcode, kds, v);
+}
+#endif
 /*
  * the row's variables are assembled: convert the numeric columns the program reads as fixed point
  * (the conversion raises nothing here -- a row the qual drops must not send the chunk back; whoever
@@ -1474,8 +1526,9 @@ gpupreagg_dense_joined(kern_gpupreagg *kgpreagg,
 				val = *(const pg_##NAME##_base_t *)(recs + (size_t)reclen * slot + recoff_##attno);	\
 			KV.KVAR_##attno = pg_##NAME##_make(val, ((words[0] >> recbit_##attno) & 1u) != 0);	\
 		}																		\
-		else																	\
-			KV.KVAR_##attno = STROM_COLUMN_REF(NAME, val_##attno, nul_##attno, outer_row);
+		else	/* (a text column's offset becomes the datum's address, checked: errors go to the row) */	\
+			KV.KVAR_##attno = gpupreagg_outer_datum(&errcode, kds,				\
+				STROM_COLUMN_REF(NAME, val_##attno, nul_##attno, outer_row));
 		STROM_KVAR_LIST_GROUPING(X)
 		STROM_KVARS_FINISH(KV);
 		if (nsplits > 1)
@@ -1755,6 +1808,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 						: pg_##NAME##_make(T.v_##attno[k][j], !((T.nn_##attno[k] >> j) & 1)));
 					STROM_KVAR_LIST(X)
 #undef X
+					/* (text offsets -> addresses; what that raises is a qual error: the row stays live) */
+					GPUPREAGG_OUTER_QUAL_VARS(KV, qerr);
 					STROM_KVARS_FINISH(KV);
 					pg_bool_t	rc = gpupreagg_qual_eval(&qerr, KP, KV);
 					live = !(qerr == StromError_Success && !EVAL(rc));
@@ -1864,6 +1919,7 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 				{
 					strom_kvars	KV;
 					gpupreagg_tile_row(KV, T, k, j);
+					GPUPREAGG_OUTER_ROW_VARS(KV);	/* (text offsets -> addresses; errors are the row's) */
 					STROM_KVARS_FINISH(KV);
 #if GPUPREAGG_ABLATE & 1
 					/* (measurement only: nothing is accumulated) */
@@ -1873,12 +1929,12 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 #endif
 #if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
 					if (PACKED)
-						gpupreagg_packed_row(lds, ctl, pk, KP, KV, gid_lo, G, param_error, &chunk_status, my_slab,
+						gpupreagg_packed_row(lds, ctl, pk, KP, KV, gid_lo, G, GPUPREAGG_ROW_ERROR, &chunk_status, my_slab,
 											 (qual_ok[k] >> j) & 1);
 					else
 #endif
 						gpupreagg_dense_row(lds, ctl, L, KP, KV, gid_lo, G, NREP, rep,
-											param_error, &chunk_status, summag, rowflags, (qual_ok[k] >> j) & 1);
+											GPUPREAGG_ROW_ERROR, &chunk_status, summag, rowflags, (qual_ok[k] >> j) & 1);
 				}
 			}
 		}
@@ -2258,6 +2314,8 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 						: pg_##NAME##_make(T.v_##attno[k][j], !((T.nn_##attno[k] >> j) & 1)));
 					STROM_KVAR_LIST(X)
 #undef X
+					/* (text offsets -> addresses; what that raises is a qual error: the row stays live) */
+					GPUPREAGG_OUTER_QUAL_VARS(KV, qerr);
 					STROM_KVARS_FINISH(KV);
 					pg_bool_t	rc = gpupreagg_qual_eval(&qerr, KP, KV);
 					live = !(qerr == StromError_Success && !EVAL(rc));
@@ -2328,15 +2386,16 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 				{
 					strom_kvars	KV;
 					gpupreagg_tile_row(KV, T, k, j);
+					GPUPREAGG_OUTER_ROW_VARS(KV);	/* (text offsets -> addresses; errors are the row's) */
 					STROM_KVARS_FINISH(KV);
 #if defined(GPUPREAGG_PACKABLE) && GPUPREAGG_PACKABLE
 					if (PACKED)
-						gpupreagg_packed_row(lds, ctl, pk, KP, KV, gid_lo, G, param_error, &chunk_status, my_slab,
+						gpupreagg_packed_row(lds, ctl, pk, KP, KV, gid_lo, G, GPUPREAGG_ROW_ERROR, &chunk_status, my_slab,
 											 (qual_ok[k] >> j) & 1);
 					else
 #endif
 						gpupreagg_dense_row(lds, ctl, L, KP, KV, gid_lo, G, NREP, rep,
-											param_error, &chunk_status, summag, rowflags, (qual_ok[k] >> j) & 1);
+											GPUPREAGG_ROW_ERROR, &chunk_status, summag, rowflags, (qual_ok[k] >> j) & 1);
 				}
 			}
 		}

@@ -94,6 +94,26 @@ strom_varlena_payload(cl_ulong datum, cl_int *p_len)
 		return pg_##NAME##_from_addr(errcode, (const char *)kds + v.value, -1);	\
 	}																			\
 	STROM_DEVICE pg_##NAME##_t													\
+	pg_##NAME##_from_offset(cl_int *errcode, const kern_data_store *kds,		\
+							pg_##NAME##_t v)									\
+	{																		\
+		/* pg_<type>_from_column for a caller whose variables number a VIRTUAL	\
+		 * relation (the fused join-and-aggregate kernels: attno is no chunk	\
+		 * column there; the host has proven attlen == -1 for the chunk column	\
+		 * it maps to).  The offset, then the datum by its own length, inside	\
+		 * the chunk; then the header.  No byte behind an offset is read before	\
+		 * the offset is checked. */											\
+		if (v.isnull || v.value == 0)											\
+			return pg_##NAME##_make(0UL, true);									\
+		if (v.value >= kds->length ||											\
+			v.value + strom_varsize_any((const char *)kds + v.value) > kds->length)	\
+		{																	\
+			STROM_SET_ERROR(errcode, StromError_DataStoreCorruption);			\
+			return pg_##NAME##_make(0UL, true);									\
+		}																	\
+		return pg_##NAME##_from_addr(errcode, (const char *)kds + v.value, -1);	\
+	}																		\
+	STROM_DEVICE pg_##NAME##_t													\
 	pg_##NAME##_param(const kern_parambuf *kparams,								\
 					  cl_int *errcode, cl_uint param_id)						\
 	{																			\

@@ -108,6 +108,8 @@ struct strom_gpupreagg {
 	/* join-as-a-lookup: the program built FOR a column mapping (lookup_program), by its defines */
 	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (lookup_mapping_program) */
 	char			   *d_export_spec = nullptr;	/* preagg_export_spec of this table (fetch on the device) */
+	/* the program's text / character(n) variables: { attno, type oid } (its STROM_KVARLENA_LIST) */
+	std::vector<std::pair<int, int>> varlena_vars;
 
 	/* the LDS / slab image of this session's aggregates (strom_ctl.h): section 0 = flags,
 	 * 1+a = values of aggregate a, 1+naggs = total */
@@ -692,6 +694,31 @@ star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs, bool c
 		return nullptr;
 	sess->lookup_programs[defs] = std::make_pair(key, prog);
 	return prog;
+}
+
+/*
+ * The fused join-and-aggregate kernels and a program with text / character(n) variables: the
+ * kernels stream the outer chunk's column arrays and turn a text column's 8-byte offsets into
+ * addresses (strom_gpupreagg.h: strom_kvars_from_outer_column), which is right only when every
+ * such variable IS a varlena column of the outer chunk -- it maps to depth 0, the mapping names
+ * the variable's own type, and the chunk column has attlen == -1 (oh: the chunk's downloaded
+ * head).  A dimension cannot serve one: slot records hold fixed-width values.  Anything else is
+ * the caller's BadRequest.  (A program whose only text values are constants or parameters has no
+ * such variable and nothing to map: their datums live in the kern_parambuf.)
+ */
+bool
+varlena_mapping_ok(const strom_gpupreagg *sess, int ncols, const int32_t *src_depth,
+				   const int32_t *src_colidx, const int32_t *type_oids, const kern_data_store *oh)
+{
+	for (auto &v : sess->varlena_vars)
+	{
+		int		i = v.first - 1;
+		if (i >= ncols || src_depth[i] != 0 || type_oids[i] != v.second ||
+			src_colidx[i] < 0 || src_colidx[i] >= (int)oh->ncols ||
+			oh->colmeta[src_colidx[i]].attlen != -1)
+			return false;
+	}
+	return true;
 }
 
 /*
@@ -2054,6 +2081,18 @@ gpupreagg_session_new(strom_devprog_key key,
 		const char *src = prog->source.c_str();
 		const char *lst = strstr(src, "#define GPUPREAGG_PACK_LIST(X)");
 		sess->numeric_aggs = (strstr(src, "#define GPUPREAGG_NUMERIC_AGGS 1") != nullptr);
+		if (const char *vl = strstr(src, "#define STROM_KVARLENA_LIST(X)"))
+		{
+			/* (codegen.cpp: codegen_var_list -- X(attno,text) / X(attno,bpcharn)) */
+			const char *eol = strchr(vl, '\n');
+			for (const char *p = strstr(vl, " X("); p && (!eol || p < eol); p = strstr(p + 1, " X("))
+			{
+				int		attno = 0;
+				char	name[16] = "";
+				if (sscanf(p, " X(%d,%15[a-z0-9])", &attno, name) == 2 && attno >= 1)
+					sess->varlena_vars.emplace_back(attno, !strcmp(name, "text") ? STROM_TEXTOID : STROM_BPCHARNOID);
+			}
+		}
 		sess->packable = (strstr(src, "#define GPUPREAGG_PACKABLE 1") != nullptr && lst != nullptr);
 		if (lst)
 		{
@@ -2408,8 +2447,6 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 		 * join program would silently not be applied */
 		(lookup && has_outer_qual) ||
 		key_attno < 1 || outer->head.format != KDS_FORMAT_COLUMN ||
-		/* (these kernels stream the outer columns; text variables take the plain fold) */
-		(sess->prog->extra_flags & DEVTYPE_IS_VARLENA) != 0 ||
 		outer->dindex != sess->dev->dindex || tbl_dindex != sess->dev->dindex)
 	{
 		/* needs: a finished join with STROM_RESULTS_ON_DEVICE, one inner relation
@@ -2429,6 +2466,12 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 		return nullptr;
 	}
 	const kern_data_store *oh = (const kern_data_store *)ohead.data();
+	/* (these kernels stream the outer columns: a text variable must be one of them) */
+	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
 	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_joined_map), 0);
 	gpupreagg_joined_map *jm = (gpupreagg_joined_map *)img->data();
 	jm->ncols = ncols;
@@ -2444,6 +2487,7 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 			case STROM_BOOLOID: case STROM_BPCHAROID:	attlen = 1; break;
 			case STROM_INT2OID:							attlen = 2; break;
 			case STROM_INT4OID: case STROM_FLOAT4OID: case STROM_DATEOID:	attlen = 4; break;
+			case STROM_TEXTOID: case STROM_BPCHARNOID:	attlen = -1; break;		/* (outer columns only) */
 			default:									attlen = 8; break;
 		}
 		jm->c[i].depth = src_depth[i];
@@ -2617,8 +2661,6 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 		ntbls < 1 || ntbls > STROM_LOOKUP_STAR_MAXRELS ||
 		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids ||
 		outer->head.format != KDS_FORMAT_COLUMN ||
-		/* (these kernels stream the outer columns; text variables take the plain fold) */
-		(sess->prog->extra_flags & DEVTYPE_IS_VARLENA) != 0 ||
 		outer->dindex != sess->dev->dindex)
 		return nullptr;
 	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_star_map), 0);
@@ -2649,6 +2691,9 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
 		return nullptr;
 	const kern_data_store *oh = (const kern_data_store *)ohead.data();
+	/* (these kernels stream the outer columns: a text variable must be one of them) */
+	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
+		return nullptr;
 	auto attlen_of = [](int32_t type_oid) -> int {
 		switch (type_oid < 0 ? -type_oid : type_oid)
 		{
@@ -2668,8 +2713,11 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 	{
 		sm->c[i].depth = src_depth[i];
 		sm->c[i].col = src_colidx[i];
+		/* (a text / character(n) column is an outer column's offset array: attlen -1) */
+		bool	varlena = (type_oids[i] == STROM_TEXTOID || type_oids[i] == STROM_BPCHARNOID);
 		if (src_depth[i] == 0 &&
-			(src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen_of(type_oids[i])))
+			(src_colidx[i] >= outer_ncols ||
+			 oh->colmeta[src_colidx[i]].attlen != (varlena ? -1 : attlen_of(type_oids[i]))))
 		{
 			*p_errcode = StromError_DataStoreCorruption;
 			return nullptr;

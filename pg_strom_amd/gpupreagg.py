@@ -227,11 +227,13 @@ class GpuPreAgg(object):
         """fold the rows of a join straight from its result pairs
         (strom_submit_gpupreagg_joined): join_pending = join.submit(chunk, flags=
         STROM_RESULTS_ON_DEVICE) not yet collected; columns as in join_to_column.
-        The join's device results pass to this request."""
-        from .kds import SQL_TYPES
+        The join's device results pass to this request.  A text / character(n) variable of the
+        program must be a column of 'chunk': mapped at depth 0, as "text" / "character", onto a
+        varlena column (BadRequest otherwise; a dimension serves fixed-width columns only)."""
+        from .kds import column_type_oid
         depth = np.array([d for d, _, _ in columns], dtype=np.int32)
         colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([SQL_TYPES[t][0] for _, _, t in columns], dtype=np.int32)
+        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_joined(self.session, join_pending[0], join.table, chunk.handle,
                                                  len(columns), depth.ctypes.data, colidx.ctypes.data,
@@ -243,11 +245,15 @@ class GpuPreAgg(object):
     def submit_lookup(self, join, chunk, columns):
         """fact JOIN dim GROUP BY in one pass (strom_submit_gpupreagg_lookup): the join
         is a lookup in the aggregate's own pass over the resident COLUMN chunk; 'join' only
-        lends its hash table.  columns as in join_to_column."""
-        from .kds import SQL_TYPES
+        lends its hash table.  columns as in join_to_column.  A text / character(n) variable of
+        the program (in the qual, in an aggregate's argument) must be a fact column: mapped at depth
+        0, as "text" / "character", onto a varlena column of 'chunk' -- BadRequest otherwise, a
+        dimension serves fixed-width columns only.  An unreadable (compressed / external) datum in
+        a row that has a partner sends the chunk back (status 2, nothing folded)."""
+        from .kds import column_type_oid
         depth = np.array([d for d, _, _ in columns], dtype=np.int32)
         colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([SQL_TYPES[t][0] for _, _, t in columns], dtype=np.int32)
+        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_lookup(self.session, join.table, chunk.handle,
                                                  len(columns), depth.ctypes.data, colidx.ctypes.data,
@@ -260,11 +266,12 @@ class GpuPreAgg(object):
         """fact JOIN dim1 JOIN dim2 ... GROUP BY in one pass (strom_submit_gpupreagg_lookup_star):
         joins[d - 1] lends relation d's hash table (its program names the outer column that joins
         it); columns as in join_to_column with depth 0 .. len(joins).  An inner join: a row is
-        folded only if every relation has a partner."""
-        from .kds import SQL_TYPES
+        folded only if every relation has a partner.  Text / character(n) variables as in
+        submit_lookup: fact columns only, mapped at depth 0 under their own type."""
+        from .kds import column_type_oid
         depth = np.array([d for d, _, _ in columns], dtype=np.int32)
         colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([SQL_TYPES[t][0] for _, _, t in columns], dtype=np.int32)
+        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
         tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_lookup_star(self.session, tbls, len(joins), chunk.handle,

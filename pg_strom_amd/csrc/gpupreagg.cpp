@@ -91,9 +91,9 @@ struct strom_gpupreagg {
 	/*
 	 * integer sums never wrap (strom_gpupreagg.h): per aggregate the static magnitude bound
 	 * the code generator found (GPUPREAGG_SUMBITS_<a>: 0 not an integer sum, 1..63 bits, 64
-	 * none), the OR of the static bounds (preset in every request's kern_gpupreagg), the
-	 * aggregates whose sums are 128 bits wide in the resident table, and the program built
-	 * with GPUPREAGG_CHECKED that folds a chunk whose range proof failed
+	 * none), the OR of the static bounds (preset in every request's kern_gpupreagg) and the
+	 * aggregates whose sums are 128 bits wide in the resident table.  (A chunk whose range proof
+	 * failed is folded by the program built with GPUPREAGG_CHECKED: checked_program)
 	 */
 	std::vector<int>	sumbits;
 	std::vector<std::string> sumbound;	/* sumbits 66: the code generator's bound formula (eval_sum_bound) */
@@ -101,12 +101,11 @@ struct strom_gpupreagg {
 	bool				sums_measured = false;	/* an integer sum without a static bound */
 	std::vector<int>	intsum_of;			/* aggregate -> index among the integer sums, or -1 */
 	int					nintsums = 0;
-	strom_devprog_key	key_checked = 0;
-	Program			   *prog_checked = nullptr;
 	std::atomic<cl_uint> checked_folds{0};	/* (reported: chunks that took the checked program) */
 	cl_uint				sum_turn = 0;		/* hashed: folds queued so far; its parity is the next fold's (gpupreagg_hash_sum_account) */
-	/* join-as-a-lookup: the program built FOR a column mapping (lookup_program), by its defines */
-	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (lookup_mapping_program) */
+	/* the session's source built behind a define block -- FOR a column mapping (lookup_mapping_program,
+	 * star_mapping_program), with GPUPREAGG_CHECKED (checked_program) -- by that block */
+	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (program_with_defines) */
 	char			   *d_export_spec = nullptr;	/* preagg_export_spec of this table (fetch on the device) */
 	/* the program's text / character(n) variables: { attno, type oid } (its STROM_KVARLENA_LIST) */
 	std::vector<std::pair<int, int>> varlena_vars;
@@ -141,10 +140,12 @@ session_quiesce(strom_gpupreagg *sess)
 	return rc;
 }
 
+/* bytes of a fixed-width value of this type: the one width table of this file.  (A column mapping
+ * may name a type by its negative oid -- strom_hip.h: "that type, no zone map needed".) */
 int
 type_length(int type_oid)
 {
-	switch (type_oid)
+	switch (type_oid < 0 ? -type_oid : type_oid)
 	{
 		case STROM_BOOLOID: case STROM_BPCHAROID:	return 1;
 		case STROM_INT2OID:							return 2;
@@ -490,32 +491,44 @@ packed_plan(strom_gpupreagg *sess, hipFunction_t fn_packed, const kern_coldir *c
 	return &it->second;
 }
 
-#define REQ_CHECK(call, what)												\
+#define REQ_CHECK_OR(call, what, failed)										\
 	do {																	\
 		hipError_t __rc = (call);											\
 		if (__rc != hipSuccess)												\
 		{																	\
 			task_fail(task, hip_errcode(__rc, what));						\
-			return;															\
+			return failed;													\
 		}																	\
 	} while (0)
+#define REQ_CHECK(call, what)	REQ_CHECK_OR(call, what, )
+
+/* where a request's rows come from: that decides the fold kernel, its arguments and the control
+ * block it reads (fold_kernels, queue_fold_and_merge, map_column_source) */
+enum preagg_kind {
+	PREAGG_PLAIN,			/* the chunk's rows, or a row map's */
+	PREAGG_JOINED,			/* a finished GpuHashJoin's result pairs (strom_submit_gpupreagg_joined) */
+	PREAGG_LOOKUP,			/* the chunk's rows, the join a lookup in the aggregate's pass (..._lookup) */
+	PREAGG_STAR,			/* ... a lookup in every relation of a star (..._lookup_star) */
+};
 
 struct preagg_request {
-	strom_gpupreagg	   *sess;
-	const kern_data_store *kds;
-	strom_dstore	   *kds_dev;
-	const kern_row_map *krowmap;
-	strom_rowmap	   *rowmap_dev;		/* device-resident row map (chained operators) */
-	uint32_t			format;
-	uint32_t			nrows;
-	/* rows = a finished GpuHashJoin's result pairs (strom_submit_gpupreagg_joined) */
+	strom_gpupreagg	   *sess = nullptr;
+	const kern_data_store *kds = nullptr;
+	strom_dstore	   *kds_dev = nullptr;
+	const kern_row_map *krowmap = nullptr;
+	strom_rowmap	   *rowmap_dev = nullptr;	/* device-resident row map (chained operators) */
+	uint32_t			format = 0;
+	uint32_t			nrows = 0;
+	preagg_kind			kind = PREAGG_PLAIN;
+	/* joined: the join's result pairs */
 	const void		   *joined_results = nullptr;	/* device kern_resultbuf */
 	void			   *joined_buffer = nullptr;	/* the join's device image, owned by this request now */
-	bool				lookup = false;				/* no result pairs: the join is a lookup in the aggregate's pass */
-	Program			   *prog = nullptr;				/* lookup: the session's program built for this column mapping */
-	std::shared_ptr<std::vector<char>> joined_map;	/* a gpupreagg_joined_map; star: a gpupreagg_star_map */
-	bool				star = false;				/* lookup over a star of relations (gpupreagg_dense_lookup_star) */
-	std::string			star_defs;					/* ... the define block 'prog' was built with */
+	/* the program to fold with when it is not the session's own: the one built for this column
+	 * mapping (lookup, star), or the checked one of a retry (checked_program) */
+	Program			   *prog = nullptr;
+	/* joined, lookup: a gpupreagg_joined_map; star: a gpupreagg_star_map (write_joined_map / write_star_map) */
+	std::shared_ptr<std::vector<char>> map;
+	std::string			star_defs;					/* star: the define block 'prog' was built with */
 	/* hashed, exact fold (gpupreagg_hashed_exact): 'sess' is a scratch session of this one */
 	strom_gpupreagg	   *exact_parent = nullptr;
 };
@@ -606,39 +619,59 @@ eval_sum_bound(const std::string &formula, const kern_coldir *cd, cl_uint ncd)
 	return bits;
 }
 
-/*
- * join-as-a-lookup: the session's source built FOR a column mapping -- which virtual column is an
- * inner one, the slot records' length and form, the key's width become compile-time constants
- * (strom_gpupreagg.h: gpupreagg_dense_lookup_body says what that is worth), and only the lookup
- * and merge kernels are built.  One program per distinct mapping, kept with the session; the first
- * request of a mapping parks behind its build like any request behind a cold program.
- */
+/* the session's source behind a define block, as a program of its own: one per distinct block, made
+ * on first use and kept with the session.  A request parks behind its build like behind any cold program. */
 Program *
-lookup_mapping_program(strom_gpupreagg *sess, const gpupreagg_joined_map *jm)
+program_with_defines(strom_gpupreagg *sess, const std::string &defs)
 {
-	if (getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
-		return nullptr;						/* the run-time form: any mapping, no build */
-	cl_ulong	inner_mask = 0;
-	for (cl_uint i = 0; i < jm->ncols && i < GPUPREAGG_JOINED_MAXCOLS; i++)
-		if (jm->c[i].depth != 0)
-			inner_mask |= (1UL << i);
-	char		defs[512];
-	snprintf(defs, sizeof(defs),
-			 "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_LOOKUP_INNER_MASK 0x%lxUL\n"
-			 "#define GPUPREAGG_LOOKUP_RECLEN %u\n#define GPUPREAGG_LOOKUP_NARROW %u\n"
-			 "#define GPUPREAGG_LOOKUP_KEYLEN %d\n",
-			 (unsigned long)inner_mask, jm->reclen, jm->narrow ? 1u : 0u, jm->key_attlen);
 	std::lock_guard<std::mutex> g(sess->lock);
 	auto	it = sess->lookup_programs.find(defs);
 	if (it != sess->lookup_programs.end())
 		return it->second.second;
-	std::string	source = std::string(defs) + sess->prog->source;
+	std::string	source = defs + sess->prog->source;
 	strom_devprog_key key = strom_get_devprog_key(source.c_str(), sess->prog->extra_flags);
 	Program	   *prog = (key ? lookup_program(key) : nullptr);
 	if (!prog)
 		return nullptr;
 	sess->lookup_programs[defs] = std::make_pair(key, prog);
 	return prog;
+}
+
+/* the column mapping of a fused fold as build_fold_mapping found it, neutral of the control block the
+ * kernel reads (write_joined_map, write_star_map lay it out).  Lives on the submitter's stack. */
+struct fold_mapping {
+	int			ncols = 0, nrels = 0;
+	/* per column -- depth, col, recoff, nullbit, nshift / nmask / nmin: the star block's own record */
+	decltype(gpupreagg_star_map::c) c;
+	/* per relation, as parallel arrays (star_mapping_defines takes four of them as they are) */
+	int32_t		key_col[GPUPREAGG_STAR_MAXRELS];		/* outer column (0-based) that is the join key */
+	int32_t		key_attlen[GPUPREAGG_STAR_MAXRELS];
+	int32_t		reclen[GPUPREAGG_STAR_MAXRELS];
+	int32_t		narrow[GPUPREAGG_STAR_MAXRELS];
+	uint64_t	inner_mask[GPUPREAGG_STAR_MAXRELS];		/* the virtual columns the relation serves */
+	cl_long		key_min[GPUPREAGG_STAR_MAXRELS];
+	cl_uint		nslots[GPUPREAGG_STAR_MAXRELS];
+	cl_ulong	recs[GPUPREAGG_STAR_MAXRELS];			/* device address of the slot records */
+};
+
+/*
+ * join-as-a-lookup: the session's source built FOR a column mapping -- which virtual column is an
+ * inner one, the slot records' length and form, the key's width become compile-time constants
+ * (strom_gpupreagg.h: gpupreagg_dense_lookup_body says what that is worth), and only the lookup
+ * and merge kernels are built.  One program per distinct mapping (program_with_defines).
+ */
+Program *
+lookup_mapping_program(strom_gpupreagg *sess, const fold_mapping &m)
+{
+	if (getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
+		return nullptr;						/* the run-time form: any mapping, no build */
+	char		defs[512];
+	snprintf(defs, sizeof(defs),
+			 "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_LOOKUP_INNER_MASK 0x%lxUL\n"
+			 "#define GPUPREAGG_LOOKUP_RECLEN %u\n#define GPUPREAGG_LOOKUP_NARROW %u\n"
+			 "#define GPUPREAGG_LOOKUP_KEYLEN %d\n",
+			 (unsigned long)m.inner_mask[0], (unsigned)m.reclen[0], m.narrow[0] ? 1u : 0u, m.key_attlen[0]);
+	return program_with_defines(sess, defs);
 }
 
 /* the define block of a star mapping (strom_gpupreagg.h: GPUPREAGG_STAR_*); "" = no valid mapping */
@@ -672,28 +705,26 @@ star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, co
 	return defs;
 }
 
+/* star of lookups: the session's source built FOR the mapping, like lookup_mapping_program -- and ALWAYS: the
+ * star kernels have no run-time-mapping form (STROM_GPUPREAGG_LOOKUP_GENERIC is the one-table call's) */
+Program *
+star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs)
+{
+	return program_with_defines(sess, star_defs);
+}
+
 /*
- * star of lookups: the session's source built FOR the mapping, like lookup_mapping_program -- and
- * ALWAYS: the star kernels have no run-time-mapping form (STROM_GPUPREAGG_LOOKUP_GENERIC is the
- * one-table call's).  checked: the same with GPUPREAGG_CHECKED, for a chunk whose integer sums
- * the range proof did not cover (ensure_checked_program is the session's own source, which has
- * no star kernel).
+ * the program that folds a request again whose integer sums could not be proven to stay in int8
+ * (strom_gpupreagg.h, "integer sums never wrap"): built with GPUPREAGG_CHECKED, on first use --
+ * such chunks are rare.  A star's kernels live in its mapping's own program, so that is the one
+ * built again; every other kind folds with the session's own source (a lookup: by the run-time
+ * form of its kernel).
  */
 Program *
-star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs, bool checked = false)
+checked_program(const preagg_request &req)
 {
-	std::string	defs = (checked ? "#define GPUPREAGG_CHECKED 1\n" : "") + star_defs;
-	std::lock_guard<std::mutex> g(sess->lock);
-	auto	it = sess->lookup_programs.find(defs);
-	if (it != sess->lookup_programs.end())
-		return it->second.second;
-	std::string	source = defs + sess->prog->source;
-	strom_devprog_key key = strom_get_devprog_key(source.c_str(), sess->prog->extra_flags);
-	Program	   *prog = (key ? lookup_program(key) : nullptr);
-	if (!prog)
-		return nullptr;
-	sess->lookup_programs[defs] = std::make_pair(key, prog);
-	return prog;
+	return program_with_defines(req.sess, "#define GPUPREAGG_CHECKED 1\n" +
+								(req.kind == PREAGG_STAR ? req.star_defs : std::string()));
 }
 
 /*
@@ -721,25 +752,430 @@ varlena_mapping_ok(const strom_gpupreagg *sess, int ncols, const int32_t *src_de
 	return true;
 }
 
-/*
- * the program that folds a chunk whose integer sums could not be proven to stay in
- * int8 (strom_gpupreagg.h, "integer sums never wrap"): the session's own source built with
- * GPUPREAGG_CHECKED.  Made on first use -- such chunks are rare -- and kept with the session.
- */
-int
-ensure_checked_program(strom_gpupreagg *sess)
+/* virtual column i of a lookup's mapping: where it comes from; returns the mapping's column count */
+cl_uint
+map_column_source(const preagg_request &req, cl_uint i, cl_int *p_depth, cl_int *p_col)
 {
-	std::lock_guard<std::mutex> g(sess->lock);
-	if (sess->prog_checked)
-		return 0;
-	std::string	source = "#define GPUPREAGG_CHECKED 1\n" + sess->prog->source;
-	strom_devprog_key key = strom_get_devprog_key(source.c_str(), sess->prog->extra_flags);
-	Program	   *prog = (key ? lookup_program(key) : nullptr);
-	if (!prog)
-		return StromError_OutOfMemory;
-	sess->key_checked = key;
-	sess->prog_checked = prog;
+	if (req.kind == PREAGG_STAR)
+	{
+		const gpupreagg_star_map *sm = (const gpupreagg_star_map *)req.map->data();
+		*p_depth = sm->c[i].depth;
+		*p_col = sm->c[i].col;
+		return sm->ncols;
+	}
+	const gpupreagg_joined_map *jm = (const gpupreagg_joined_map *)req.map->data();
+	*p_depth = jm->c[i].depth;
+	*p_col = jm->c[i].col;
+	return jm->ncols;
+}
+
+/*
+ * launch step A -- a chunk's column directory (NULL bitmaps present?  zone maps), from the host image
+ * or the device store's snapshot.  lookup: that request's VIRTUAL columns, which its program reads -- an
+ * outer column brings its own entry, an inner one counts as "may be NULL, no zone map".  cd NULL: none.
+ */
+struct chunk_coldir {
+	const kern_coldir  *cd = nullptr;
+	cl_uint				ncols = 0;
+	std::shared_ptr<std::vector<kern_coldir>> snap;
+	std::vector<kern_coldir> virt;
+};
+
+void
+chunk_coldir_of(const kern_data_store *kds, strom_dstore *kds_dev, const preagg_request *lookup, chunk_coldir *out)
+{
+	if (kds)
+	{
+		out->cd = KERN_DATA_STORE_COLDIR(kds);
+		out->ncols = kds->ncols;
+	}
+	else if ((out->snap = dstore_coldir(kds_dev)) != nullptr)
+	{
+		out->cd = out->snap->data();
+		out->ncols = (cl_uint)out->snap->size();
+	}
+	if (!out->cd || !lookup)
+		return;
+	cl_int		depth = 0, col = 0;
+	out->virt.resize(map_column_source(*lookup, 0, &depth, &col));
+	for (cl_uint i = 0; i < out->virt.size(); i++)
+	{
+		map_column_source(*lookup, i, &depth, &col);
+		memset(&out->virt[i], 0, sizeof(kern_coldir));
+		if (depth == 0 && col >= 0 && (cl_uint)col < out->ncols)
+			out->virt[i] = out->cd[col];
+		else
+			out->virt[i].nulls_off = 1;
+	}
+	out->cd = out->virt.data();
+	out->ncols = (cl_uint)out->virt.size();
+}
+
+/* per kind, the fold kernel and its packed-accumulator variant (NULL: none); a plain request that
+ * streams a COLUMN chunk has kernels of its own (plan_fold) */
+const char *const fold_kernels[][2] = {
+	/* PREAGG_PLAIN */	{ "gpupreagg_dense_generic", nullptr },
+	/* PREAGG_JOINED */	{ "gpupreagg_dense_joined", nullptr },
+	/* PREAGG_LOOKUP */	{ "gpupreagg_dense_lookup", "gpupreagg_packed_lookup" },
+	/* PREAGG_STAR */	{ "gpupreagg_dense_lookup_star", "gpupreagg_packed_lookup_star" },
+};
+
+/*
+ * sums of PLAIN columns (GPUPREAGG_SUMBITS_<a> 65) and of expressions over decimal columns (66)
+ * over a COLUMN chunk with zone maps: bounded here, the fold does not measure them (top bit of
+ * the second word; the streaming kernels read it, the row-at-a-time ones measure as always).
+ * True when every such sum is bounded; *p_bits: bits of the largest magnitude.
+ */
+bool
+zone_sum_bound(const strom_gpupreagg *sess, const kern_coldir *cd, cl_uint ncd, cl_uint *p_bits)
+{
+	bool		all = (cd != nullptr), any = false;
+	cl_uint		zbits = 0;
+	for (size_t a = 0; all && a < sess->agg_resno.size(); a++)
+	{
+		if (sess->sumbits[a] == 66)
+		{
+			/* an expression over decimal columns: the code generator's formula */
+			int		bits = eval_sum_bound(sess->sumbound[a], cd, ncd);
+			if (bits < 0 || bits > 63)
+				all = false;			/* (no zone map -- or a bound beyond int8: measured, then checked) */
+			else
+			{
+				zbits = std::max(zbits, (cl_uint)bits);
+				any = true;
+			}
+			continue;
+		}
+		if (sess->sumbits[a] != 65)
+			continue;
+		int		col = (a < sess->pack_attno.size() ? sess->pack_attno[a] - 1 : -1);
+		if (col < 0 || col >= (int)ncd || !(cd[col].stat_flags & KDS_COLSTAT_MINMAX) ||
+			(cd[col].stat_flags & KDS_COLSTAT_ISFLOAT) || cd[col].maxval < cd[col].minval)
+			all = false;
+		else
+		{
+			zbits = std::max(zbits, zone_magbits(cd[col]));
+			any = true;
+		}
+	}
+	*p_bits = zbits;
+	return all && any;
+}
+
+/* launch step B -- how this request is folded: which kernel, packed accumulators or not, the range
+ * proof's inputs.  Host work only (packed_plan makes a role count's geometry once). */
+struct fold_plan {
+	hipFunction_t	fn = nullptr, fn_merge = nullptr;
+	bool			use_column = false;		/* a COLUMN chunk streamed as arrays: no pairs, no lookup, no row map */
+	bool			use_reg = false;		/* ... by the register / lane-private kernels */
+	strom_gpupreagg::packed_geom *packed = nullptr;
+	gpupreagg_pack_ctl pk;
+	cl_uint			magbits = 0;			/* what is known about the integer sums' inputs before the fold measures the rest */
+	bool			zone_bounded = false;
+	size_t			wg_rows = 0;
+};
+
+int
+plan_fold(Device *dev, Program *prog, const preagg_request &req, bool checked, fold_plan *plan)
+{
+	strom_gpupreagg *sess = req.sess;
+	bool		use_lookup = (req.kind == PREAGG_LOOKUP || req.kind == PREAGG_STAR);
+	int			errcode = 0;
+	const char *name = fold_kernels[req.kind][0], *name_packed = fold_kernels[req.kind][1];
+
+	plan->use_column = (req.kind == PREAGG_PLAIN && req.format == KDS_FORMAT_COLUMN &&
+						req.krowmap == nullptr && req.rowmap_dev == nullptr);
+	/* (the checked program adds in LDS with returning atomics: the LDS-atomics kernels only) */
+	plan->use_reg = (plan->use_column && sess->reg_groups != 0 && !checked);
+	if (plan->use_reg)
+		name = (sess->reg_groups == 1 ? "gpupreagg_reg1_column" : "gpupreagg_priv_column");
+	else if (plan->use_column)
+	{
+		name = "gpupreagg_dense_column";
+		name_packed = "gpupreagg_packed_column";
+	}
+	plan->fn = prog->get_function(dev, name, &errcode);
+	plan->fn_merge = plan->fn ? prog->get_function(dev, "gpupreagg_dense_merge", &errcode) : nullptr;
+	if (!plan->fn || !plan->fn_merge)
+		return errcode;
+	plan->magbits = sess->static_magbits;
+	chunk_coldir	dir;
+	bool		want_packed = (name_packed && sess->packable && sess->ctl.nsplits > 1 && !checked);
+	if (want_packed || (!checked && plan->use_column))
+		chunk_coldir_of(req.kds, req.kds_dev, use_lookup ? &req : nullptr, &dir);
+	/* packed accumulators for this chunk?  (fewer id-range roles: see packed_plan) */
+	if (want_packed)
+	{
+		int		e2 = 0;
+		hipFunction_t fn_packed = prog->get_function(dev, name_packed, &e2);
+		plan->packed = packed_plan(sess, fn_packed, dir.cd, dir.ncols, req.nrows, &plan->pk);
+		if (plan->packed)
+		{
+			plan->fn = fn_packed;
+			/* the packed fold measures nothing: the zone maps that bound its fields bound
+			 * the integer sums' inputs too */
+			for (size_t a = 0; a < sess->agg_resno.size(); a++)
+				if (sess->pack_kind[a] == 2 && sess->sumbits[a] >= 64)
+					plan->magbits = std::max(plan->magbits, zone_magbits(dir.cd[sess->pack_attno[a] - 1]));
+		}
+	}
+	/*
+	 * the range proof's inputs (strom_gpupreagg.h, "integer sums never wrap"): rows of the
+	 * request, bits of the largest input magnitude known so far, and the rows ONE work-group
+	 * folds at most -- tiles (or, row by row, blocks) are dealt round-robin to the work-groups
+	 * of a role; one unit of slack
+	 */
+	const gpupreagg_dense_ctl &g = (plan->packed ? plan->packed->ctl : sess->ctl);
+	size_t		unit = (plan->use_reg ? (size_t)256 * 4 * sess->quads
+						: (plan->use_column || use_lookup) ? (size_t)sess->block * 4 * sess->quads
+						: (size_t)sess->block);
+	size_t		units = ((size_t)req.nrows + unit - 1) / unit;
+	size_t		wgs_per_role = std::max<size_t>(1, g.nslabs / std::max<cl_uint>(1, g.nsplits));
+	plan->wg_rows = std::min<size_t>(((units + wgs_per_role - 1) / wgs_per_role + 1) * unit, 0xffffffffUL);
+	cl_uint		zbits = 0;
+	if (!plan->packed && !checked && plan->use_column && zone_sum_bound(sess, dir.cd, dir.ncols, &zbits))
+	{
+		plan->zone_bounded = true;
+		plan->magbits = std::max(plan->magbits, zbits);
+	}
 	return 0;
+}
+
+/*
+ * launch step C, the dense and the hashed launch alike -- stage and send the kern_gpupreagg image {status,
+ * sortbuf_len, pad, kern_parambuf} [+ the pack control block] on s_in, then the chunk and the row map
+ * (unless they are resident) on the task's stream
+ */
+struct sent_request {
+	char	   *stage = nullptr;		/* pinned: the image as sent; the status comes back behind it */
+	char	   *d_kg = nullptr;
+	size_t		kg_len = 0;				/* the kern_gpupreagg image alone */
+	size_t		send_len = 0;			/* ... with the pack control block */
+	const void *d_kds = nullptr;
+	const void *d_rowmap = nullptr;
+};
+
+bool
+send_request(strom_task_impl *task, const preagg_request &req, hipStream_t s_in,
+			 cl_uint magbits, size_t wg_rows, bool zone_bounded, const gpupreagg_pack_ctl *pk, sent_request *out)
+{
+	strom_gpupreagg *sess = req.sess;
+	Device	   *dev = task->dev;
+	size_t		kg_len = STROMALIGN(offsetof(kern_gpupreagg, kparams) + sess->kparams.size());
+	size_t		send_len = kg_len + (pk ? STROMALIGN(sizeof(gpupreagg_pack_ctl)) : 0);
+	char	   *stage = dev->pinned.alloc();
+	char	   *d_kg = (char *)dev->pool.alloc(send_len);
+	if (!stage || !d_kg || send_len + 64 > PinnedPool::BLOCK)
+	{
+		if (stage) dev->pinned.release(stage);
+		if (d_kg) dev->pool.release(d_kg);
+		task_fail(task, StromError_OutOfMemory);
+		return false;
+	}
+	task->pinned_blocks.push_back(stage);
+	task->main_devptr = d_kg;
+	memset(stage, 0, kg_len);
+	memcpy(stage + offsetof(kern_gpupreagg, kparams), sess->kparams.data(), sess->kparams.size());
+	kern_gpupreagg_set_chunk_words((kern_gpupreagg *)stage, req.nrows, magbits, wg_rows, zone_bounded);
+	if (pk)
+		memcpy(stage + kg_len, pk, sizeof(*pk));
+	out->stage = stage;
+	out->d_kg = d_kg;
+	out->kg_len = kg_len;
+	out->send_len = send_len;
+
+	task_event(task, s_in);								/* ev[0] */
+	REQ_CHECK_OR(hipMemcpyAsync(d_kg, stage, send_len, hipMemcpyHostToDevice, s_in),
+				 "send kern_gpupreagg", false);
+	task->pfm.num_dma_send++;
+	task->pfm.bytes_dma_send += send_len;
+	if (req.kds_dev)
+		out->d_kds = req.kds_dev->devptr;
+	else
+	{
+		size_t	kds_len = req.kds->length;
+		if (req.kds->format == KDS_FORMAT_ROW)
+			kds_len = KERN_DATA_STORE_ROWBLOCK_OFFSET(req.kds) + (size_t)BLCKSZ * req.kds->nblocks;
+		void   *p = dev->pool.alloc(kds_len);
+		if (!p)
+		{
+			task_fail(task, StromError_OutOfMemory);
+			return false;
+		}
+		task->devbufs.push_back(p);
+		REQ_CHECK_OR(hipMemcpyAsync(p, req.kds, kds_len, hipMemcpyHostToDevice, task->stream),
+					 "send kern_data_store", false);
+		task->pfm.num_dma_send++;
+		task->pfm.bytes_dma_send += kds_len;
+		out->d_kds = p;
+	}
+	out->d_rowmap = (req.rowmap_dev ? req.rowmap_dev->devptr : nullptr);
+	if (!req.rowmap_dev && req.krowmap)
+	{
+		size_t	len = offsetof(kern_row_map, rindex) + sizeof(cl_int) * (size_t)req.krowmap->nvalids;
+		void   *p = dev->pool.alloc(len);
+		if (!p)
+		{
+			task_fail(task, StromError_OutOfMemory);
+			return false;
+		}
+		task->devbufs.push_back(p);
+		REQ_CHECK_OR(hipMemcpyAsync(p, req.krowmap, len, hipMemcpyHostToDevice, task->stream),
+					 "send kern_row_map", false);
+		out->d_rowmap = p;
+	}
+	return true;
+}
+
+/* launch step D -- queue the fold behind the request head, the merge check and the merge behind the fold,
+ * and the status read-back; the session's launch_lock is held.  False: the task has failed. */
+bool
+queue_fold_and_merge(strom_task_impl *task, const preagg_request &req, Program *prog, bool checked,
+					 const fold_plan &plan, const sent_request &sent, const void *d_jmap,
+					 bool piped, hipStream_t s_in, hipStream_t s_mrg)
+{
+	strom_gpupreagg *sess = req.sess;
+	Device	   *dev = task->dev;
+	strom_gpupreagg::packed_geom *packed = plan.packed;
+
+	/* this request's slab buffer; whoever read it last must be through */
+	unsigned	turn = (sess->slab_turn++ & 1);
+	for (int b = 0; b < 2; b++)
+		if (!sess->merge_ev[b] &&
+			hipEventCreateWithFlags(&sess->merge_ev[b], hipEventDisableTiming) != hipSuccess)
+		{
+			task_fail(task, StromError_HipInternal);
+			return false;
+		}
+	if (piped)
+	{
+		hipEvent_t sent_ev = task_event(task, s_in);		/* ev[1]: head is down */
+		REQ_CHECK_OR(hipStreamWaitEvent(task->stream, sent_ev, 0), "wait for the request head", false);
+	}
+	else
+		task_event(task);									/* ev[1] */
+	if (sess->merge_ev_used[turn])
+		REQ_CHECK_OR(hipStreamWaitEvent(task->stream, sess->merge_ev[turn], 0), "wait for the slab buffer", false);
+	/* piped: the fold kernel carries its own start / stop events (see task_event_slot) */
+	bool		ext_launch = (piped && use_ext_launch());
+	hipEvent_t	ev_fold_begin = nullptr, ev_fold_done = nullptr;
+	if (piped)
+	{
+		ev_fold_begin = (ext_launch ? task_event_slot(task) : task_event(task));	/* ev[2]: the fold begins */
+		if (ext_launch)
+			ev_fold_done = task_event_slot(task);			/* ev[3] */
+		if (ext_launch && (!ev_fold_begin || !ev_fold_done))
+		{
+			task_fail(task, StromError_HipInternal);
+			return false;
+		}
+	}
+	void	   *a_kg = sent.d_kg;
+	const void *a_kds = sent.d_kds;
+	const void *a_toast = nullptr;
+	const void *a_map = sent.d_rowmap;
+	const gpupreagg_dense_ctl &lctl = (packed ? packed->ctl : sess->ctl);		/* this launch's geometry */
+	void	   *a_ctl = (packed ? packed->d_ctl : sess->d_ctl);
+	void	   *a_slabs = (packed ? packed->d_slabs : sess->d_slabs) +
+		(size_t)turn * lctl.nslabs * lctl.slab_bytes;
+	void	   *a_table = sess->table;
+	const void *a_res = req.joined_results;
+	const void *a_jmap = d_jmap;
+	const void *a_pack = sent.d_kg + sent.kg_len;
+	/* the fold kernels' parameters, every kind's in this one order: kg, [result pairs,] kds,
+	 * [toast, row map,] [column mapping,] ctl, [pack ctl,] slabs */
+	void	   *fold_args[8];
+	int			na = 0;
+	fold_args[na++] = &a_kg;
+	if (req.kind == PREAGG_JOINED)
+		fold_args[na++] = &a_res;
+	fold_args[na++] = &a_kds;
+	if (req.kind == PREAGG_PLAIN && !plan.use_column)
+	{
+		fold_args[na++] = &a_toast;
+		fold_args[na++] = &a_map;
+	}
+	if (req.kind != PREAGG_PLAIN)
+		fold_args[na++] = &a_jmap;
+	fold_args[na++] = &a_ctl;
+	if (packed)
+		fold_args[na++] = &a_pack;
+	fold_args[na++] = &a_slabs;
+	void	   *args_mrg[] = { &a_kg, &a_ctl, &a_slabs, &a_table };
+	unsigned	fold_block = (plan.use_reg ? 256 : (unsigned)sess->block);
+	unsigned	fold_lds = (unsigned)(packed ? packed->lds_bytes : sess->lds_bytes);
+	if (ext_launch)
+		REQ_CHECK_OR(hipExtModuleLaunchKernel(plan.fn, lctl.nslabs * fold_block, 1, 1, fold_block, 1, 1, fold_lds,
+											  task->stream, fold_args, nullptr, ev_fold_begin, ev_fold_done, 0),
+					 "launch gpupreagg reduction", false);
+	else
+		REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn, lctl.nslabs, 1, 1, fold_block, 1, 1, fold_lds, task->stream,
+										   fold_args, nullptr),
+					 "launch gpupreagg reduction", false);
+	if (packed)
+		task->pfm.num_kern_prep++;			/* (reported: this request took the packed path) */
+	hipEvent_t fold_done = ev_fold_done;
+	if (!ext_launch && (task->pfm.enabled || piped))
+	{
+		fold_done = task_event(task);				/* ev[2] (piped: ev[3]): main kernel done */
+		task->has_ev_proj = !piped;
+	}
+	if (piped)
+	{
+		/* the merge stream takes over: behind this fold and behind the previous merge */
+		if (!fold_done)
+		{
+			task_fail(task, StromError_HipInternal);
+			return false;
+		}
+		REQ_CHECK_OR(hipStreamWaitEvent(s_mrg, fold_done, 0), "merge waits for the fold", false);
+	}
+	if (sess->merge_ev_used[turn ^ 1])
+		REQ_CHECK_OR(hipStreamWaitEvent(s_mrg, sess->merge_ev[turn ^ 1], 0), "merge waits for the previous merge", false);
+	/* the merge kernel lays 256 threads out as GL group lanes x stripes
+	 * over the slabs (strom_gpupreagg.h) */
+	unsigned ws = 1, per_split = lctl.nslabs / lctl.nsplits;
+	while (ws < 64 && ws * 8 < per_split)
+		ws <<= 1;
+	if (lctl.merge_ws != 0)
+		ws = lctl.merge_ws;
+	unsigned gl = 256 / ws;
+	unsigned mgrid = std::min<unsigned>((lctl.ngroups + gl - 1) / gl,
+										(unsigned)dev->prop.multiProcessorCount * 8);
+	/* the slab check: numeric sums; integer sums whose chunk totals the range proof may
+	 * not cover (tier 2: the kernel leaves at once when it does) */
+	if (sess->numeric_aggs || checked ||
+		(sess->nintsums > 0 && (sess->sums_measured || sess->static_magbits > 31)))
+	{
+		/* numeric sums may leave the 64-bit form while slabs are added up: find
+		 * out BEFORE the table takes any of it (gpupreagg_dense_merge_body<CHECK>) */
+		int		e3 = 0;
+		hipFunction_t fn_check = prog->get_function(dev, "gpupreagg_dense_merge_check", &e3);
+		if (!fn_check)
+		{
+			task_fail(task, e3);
+			return false;
+		}
+		REQ_CHECK_OR(hipModuleLaunchKernel(fn_check, std::max(1u, mgrid), 1, 1, 256, 1, 1, 0,
+										   s_mrg, args_mrg, nullptr),
+					 "launch gpupreagg merge check", false);
+		task->pfm.num_kern_exec++;
+	}
+	REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_merge, std::max(1u, mgrid), 1, 1, 256, 1, 1, 0,
+									   s_mrg, args_mrg, nullptr),
+				 "launch gpupreagg merge", false);
+	task->pfm.num_kern_exec += 2;
+	REQ_CHECK_OR(hipEventRecord(sess->merge_ev[turn], s_mrg), "mark the merge", false);
+	sess->merge_ev_used[turn] = true;
+	task_event(task, s_mrg);							/* ev[2] (+1 with the fold event; piped: ev[4]) */
+	REQ_CHECK_OR(hipMemcpyAsync(sent.stage + sent.send_len, sent.d_kg + offsetof(kern_gpupreagg, status), sizeof(cl_int),
+								hipMemcpyDeviceToHost, s_mrg),
+				 "recv status", false);
+	task->pfm.num_dma_recv++;
+	task->pfm.bytes_dma_recv += sizeof(cl_int);
+	task_event(task, s_mrg);							/* ev[3] (+1; piped: ev[5]) */
+	task->ev_preagg_piped = piped;
+	return true;
 }
 
 void
@@ -747,9 +1183,9 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 {
 	strom_gpupreagg *sess = req.sess;
 	Device	   *dev = task->dev;
-	/* (a star request brings its program either way: star_mapping_program) */
-	Program	   *prog = ((checked && !req.star) ? sess->prog_checked : req.prog ? req.prog : sess->prog);
-	int			errcode = 0;
+	/* (a lookup, a star and a checked retry bring their program: lookup_mapping_program,
+	 * star_mapping_program, checked_program) */
+	Program	   *prog = (req.prog ? req.prog : sess->prog);
 
 	(void)hipSetDevice(dev->hip_id);
 	if (req.joined_buffer && !checked)
@@ -776,218 +1212,21 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 	/* one launch at a time per session: the slab turn and the event chain are ordered */
 	std::lock_guard<std::mutex> launch_guard(sess->launch_lock);
 
-	bool	use_lookup = req.lookup;
-	bool	use_joined = (req.joined_results != nullptr);
-	bool	use_column = (!use_joined && !use_lookup && req.format == KDS_FORMAT_COLUMN &&
-						  req.krowmap == nullptr && req.rowmap_dev == nullptr);
-	/* (the checked program adds in LDS with returning atomics: the LDS-atomics kernels only) */
-	bool	use_reg = (use_column && sess->reg_groups != 0 && !checked);
-	hipFunction_t fn = prog->get_function(dev, req.star ? "gpupreagg_dense_lookup_star"
-										  : use_lookup ? "gpupreagg_dense_lookup"
-										  : use_joined ? "gpupreagg_dense_joined"
-										  : use_reg ? (sess->reg_groups == 1 ? "gpupreagg_reg1_column"
-																			  : "gpupreagg_priv_column")
-										  : use_column ? "gpupreagg_dense_column"
-										  : "gpupreagg_dense_generic", &errcode);
-	hipFunction_t fn_merge = fn ? prog->get_function(dev, "gpupreagg_dense_merge", &errcode) : nullptr;
-	if (!fn || !fn_merge)
+	fold_plan	plan;
+	int			errcode = plan_fold(dev, prog, req, checked, &plan);
+	if (errcode != 0)
 	{
 		task_fail(task, errcode);
 		return;
 	}
-	/* what is known about the integer sums' inputs before the fold measures the rest */
-	cl_uint		magbits = sess->static_magbits;
-	/* packed accumulators for this chunk?  (fewer id-range roles: see packed_plan) */
-	gpupreagg_pack_ctl	pk;
-	strom_gpupreagg::packed_geom *packed = nullptr;
-	if ((use_lookup || (use_column && !use_reg)) && sess->packable && sess->ctl.nsplits > 1 && !checked)
-	{
-		int		e2 = 0;
-		hipFunction_t fn_packed = prog->get_function(dev, req.star ? "gpupreagg_packed_lookup_star"
-													 : use_lookup ? "gpupreagg_packed_lookup"
-													 : "gpupreagg_packed_column", &e2);
-		std::shared_ptr<std::vector<kern_coldir>> snap;
-		std::vector<kern_coldir> virt;
-		const kern_coldir *coldir = nullptr;
-		cl_uint		ncols = 0;
-		if (req.kds)
-		{
-			coldir = KERN_DATA_STORE_COLDIR(req.kds);
-			ncols = req.kds->ncols;
-		}
-		else if ((snap = dstore_coldir(req.kds_dev)) != nullptr)
-		{
-			coldir = snap->data();
-			ncols = (cl_uint)snap->size();
-		}
-		if (use_lookup && coldir)
-		{
-			/* the program's columns are virtual: an outer column brings its own
-			 * directory entry, an inner column counts as "may be NULL, no zone map" */
-			const gpupreagg_joined_map *jm = (const gpupreagg_joined_map *)req.joined_map->data();
-			const gpupreagg_star_map *sm = (const gpupreagg_star_map *)req.joined_map->data();
-			cl_uint		nvirt = (req.star ? sm->ncols : jm->ncols);
-			virt.resize(nvirt);
-			for (cl_uint i = 0; i < nvirt; i++)
-			{
-				cl_int		depth = (req.star ? sm->c[i].depth : jm->c[i].depth);
-				cl_int		col = (req.star ? sm->c[i].col : jm->c[i].col);
-				memset(&virt[i], 0, sizeof(kern_coldir));
-				if (depth == 0 && col >= 0 && (cl_uint)col < ncols)
-					virt[i] = coldir[col];
-				else
-					virt[i].nulls_off = 1;
-			}
-			coldir = virt.data();
-			ncols = nvirt;
-		}
-		packed = packed_plan(sess, fn_packed, coldir, ncols, req.nrows, &pk);
-		if (packed)
-		{
-			fn = fn_packed;
-			/* the packed fold measures nothing: the zone maps that bound its fields bound
-			 * the integer sums' inputs too */
-			for (size_t a = 0; a < sess->agg_resno.size(); a++)
-				if (sess->pack_kind[a] == 2 && sess->sumbits[a] >= 64)
-					magbits = std::max(magbits, zone_magbits(coldir[sess->pack_attno[a] - 1]));
-		}
-	}
-	/* kern_gpupreagg image: {status, sortbuf_len, pad, kern_parambuf} [+ the pack control block] */
-	size_t	kg_len = STROMALIGN(offsetof(kern_gpupreagg, kparams) + sess->kparams.size());
-	size_t	send_len = kg_len + (packed ? STROMALIGN(sizeof(gpupreagg_pack_ctl)) : 0);
-	char   *stage = dev->pinned.alloc();
-	char   *d_kg = (char *)dev->pool.alloc(send_len);
-	if (!stage || !d_kg || send_len + 64 > PinnedPool::BLOCK)
-	{
-		if (stage) dev->pinned.release(stage);
-		if (d_kg) dev->pool.release(d_kg);
-		task_fail(task, StromError_OutOfMemory);
+	sent_request sent;
+	if (!send_request(task, req, s_in, plan.magbits, plan.wg_rows, plan.zone_bounded,
+					  plan.packed ? &plan.pk : nullptr, &sent))
 		return;
-	}
-	task->pinned_blocks.push_back(stage);
-	task->main_devptr = d_kg;
-	memset(stage, 0, kg_len);
-	memcpy(stage + offsetof(kern_gpupreagg, kparams), sess->kparams.data(), sess->kparams.size());
-	{
-		/*
-		 * the range proof's inputs (strom_gpupreagg.h, "integer sums never wrap"): rows of the
-		 * request, bits of the largest input magnitude known so far, and the rows ONE work-group
-		 * folds at most -- tiles (or, row by row, blocks) are dealt round-robin to the work-groups
-		 * of a role; one unit of slack
-		 */
-		const gpupreagg_dense_ctl &g = (packed ? packed->ctl : sess->ctl);
-		size_t		unit = (use_reg ? (size_t)256 * 4 * sess->quads
-							: (use_column || use_lookup) ? (size_t)sess->block * 4 * sess->quads
-							: (size_t)sess->block);
-		size_t		units = ((size_t)req.nrows + unit - 1) / unit;
-		size_t		wgs_per_role = std::max<size_t>(1, g.nslabs / std::max<cl_uint>(1, g.nsplits));
-		size_t		wg_rows = std::min<size_t>(((units + wgs_per_role - 1) / wgs_per_role + 1) * unit, 0xffffffffUL);
-		/*
-		 * sums of PLAIN columns (GPUPREAGG_SUMBITS_<a> 65) over a COLUMN chunk with zone maps: bounded
-		 * here, the fold does not measure them (top bit of the second word; the streaming kernels
-		 * read it, the row-at-a-time ones measure as always)
-		 */
-		bool		zone_bounded = false;
-		if (!packed && !checked && (use_column || use_reg))
-		{
-			std::shared_ptr<std::vector<kern_coldir>> snap;
-			const kern_coldir *cd = nullptr;
-			cl_uint		ncd = 0;
-			if (req.kds)
-			{
-				cd = KERN_DATA_STORE_COLDIR(req.kds);
-				ncd = req.kds->ncols;
-			}
-			else if ((snap = dstore_coldir(req.kds_dev)) != nullptr)
-			{
-				cd = snap->data();
-				ncd = (cl_uint)snap->size();
-			}
-			bool		all = (cd != nullptr), any = false;
-			cl_uint		zbits = 0;
-			for (size_t a = 0; all && a < sess->agg_resno.size(); a++)
-			{
-				if (sess->sumbits[a] == 66)
-				{
-					/* an expression over decimal columns: the code generator's formula */
-					int		bits = (cd ? eval_sum_bound(sess->sumbound[a], cd, ncd) : -1);
-					if (bits < 0 || bits > 63)
-						all = false;			/* (no zone map -- or a bound beyond int8: measured, then checked) */
-					else
-					{
-						zbits = std::max(zbits, (cl_uint)bits);
-						any = true;
-					}
-					continue;
-				}
-				if (sess->sumbits[a] != 65)
-					continue;
-				int		col = (a < sess->pack_attno.size() ? sess->pack_attno[a] - 1 : -1);
-				if (col < 0 || col >= (int)ncd || !(cd[col].stat_flags & KDS_COLSTAT_MINMAX) ||
-					(cd[col].stat_flags & KDS_COLSTAT_ISFLOAT) || cd[col].maxval < cd[col].minval)
-					all = false;
-				else
-				{
-					zbits = std::max(zbits, zone_magbits(cd[col]));
-					any = true;
-				}
-			}
-			if (all && any)
-			{
-				zone_bounded = true;
-				magbits = std::max(magbits, zbits);
-			}
-		}
-		kern_gpupreagg_set_chunk_words((kern_gpupreagg *)stage, req.nrows, magbits, wg_rows, zone_bounded);
-	}
-	if (packed)
-		memcpy(stage + kg_len, &pk, sizeof(pk));
-
-	task_event(task, s_in);								/* ev[0] */
-	REQ_CHECK(hipMemcpyAsync(d_kg, stage, send_len, hipMemcpyHostToDevice, s_in),
-			  "send kern_gpupreagg");
-	task->pfm.num_dma_send++;
-	task->pfm.bytes_dma_send += send_len;
-	const void *d_kds;
-	if (req.kds_dev)
-		d_kds = req.kds_dev->devptr;
-	else
-	{
-		size_t	kds_len = req.kds->length;
-		if (req.kds->format == KDS_FORMAT_ROW)
-			kds_len = KERN_DATA_STORE_ROWBLOCK_OFFSET(req.kds) + (size_t)BLCKSZ * req.kds->nblocks;
-		void   *p = dev->pool.alloc(kds_len);
-		if (!p)
-		{
-			task_fail(task, StromError_OutOfMemory);
-			return;
-		}
-		task->devbufs.push_back(p);
-		REQ_CHECK(hipMemcpyAsync(p, req.kds, kds_len, hipMemcpyHostToDevice, task->stream),
-				  "send kern_data_store");
-		task->pfm.num_dma_send++;
-		task->pfm.bytes_dma_send += kds_len;
-		d_kds = p;
-	}
-	const void *d_rowmap = (req.rowmap_dev ? req.rowmap_dev->devptr : nullptr);
-	if (!req.rowmap_dev && req.krowmap)
-	{
-		size_t	len = offsetof(kern_row_map, rindex) + sizeof(cl_int) * (size_t)req.krowmap->nvalids;
-		void   *p = dev->pool.alloc(len);
-		if (!p)
-		{
-			task_fail(task, StromError_OutOfMemory);
-			return;
-		}
-		task->devbufs.push_back(p);
-		REQ_CHECK(hipMemcpyAsync(p, req.krowmap, len, hipMemcpyHostToDevice, task->stream),
-				  "send kern_row_map");
-		d_rowmap = p;
-	}
 	void   *d_jmap = nullptr;
-	if (use_joined || use_lookup)
+	if (req.kind != PREAGG_PLAIN)
 	{
-		d_jmap = dev->pool.alloc(req.joined_map->size());
+		d_jmap = dev->pool.alloc(req.map->size());
 		if (!d_jmap)
 		{
 			task_fail(task, StromError_OutOfMemory);
@@ -995,141 +1234,14 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 		}
 		task->devbufs.push_back(d_jmap);
 		/* small and pageable: a synchronous copy keeps the source alive */
-		REQ_CHECK(hipMemcpy(d_jmap, req.joined_map->data(), req.joined_map->size(), hipMemcpyHostToDevice),
+		REQ_CHECK(hipMemcpy(d_jmap, req.map->data(), req.map->size(), hipMemcpyHostToDevice),
 				  "send joined map");
 	}
-	/* this request's slab buffer; whoever read it last must be through */
-	unsigned	turn = (sess->slab_turn++ & 1);
-	for (int b = 0; b < 2; b++)
-		if (!sess->merge_ev[b] &&
-			hipEventCreateWithFlags(&sess->merge_ev[b], hipEventDisableTiming) != hipSuccess)
-		{
-			task_fail(task, StromError_HipInternal);
-			return;
-		}
-	if (piped)
-	{
-		hipEvent_t sent = task_event(task, s_in);			/* ev[1]: head is down */
-		REQ_CHECK(hipStreamWaitEvent(task->stream, sent, 0), "wait for the request head");
-	}
-	else
-		task_event(task);									/* ev[1] */
-	if (sess->merge_ev_used[turn])
-		REQ_CHECK(hipStreamWaitEvent(task->stream, sess->merge_ev[turn], 0), "wait for the slab buffer");
-	/* piped: the fold kernel carries its own start / stop events (see task_event_slot) */
-	bool		ext_launch = (piped && use_ext_launch());
-	hipEvent_t	ev_fold_begin = nullptr, ev_fold_done = nullptr;
-	if (piped)
-	{
-		ev_fold_begin = (ext_launch ? task_event_slot(task) : task_event(task));	/* ev[2]: the fold begins */
-		if (ext_launch)
-			ev_fold_done = task_event_slot(task);			/* ev[3] */
-		if (ext_launch && (!ev_fold_begin || !ev_fold_done))
-		{
-			task_fail(task, StromError_HipInternal);
-			return;
-		}
-	}
-	{
-		void	   *a_kg = d_kg;
-		const void *a_kds = d_kds;
-		const void *a_toast = nullptr;
-		const void *a_map = d_rowmap;
-		const gpupreagg_dense_ctl &lctl = (packed ? packed->ctl : sess->ctl);		/* this launch's geometry */
-		void	   *a_ctl = (packed ? packed->d_ctl : sess->d_ctl);
-		void	   *a_slabs = (packed ? packed->d_slabs : sess->d_slabs) +
-			(size_t)turn * lctl.nslabs * lctl.slab_bytes;
-		void	   *a_table = sess->table;
-		const void *a_res = req.joined_results;
-		const void *a_jmap = d_jmap;
-		const void *a_pack = d_kg + kg_len;
-		void	   *args_col[] = { &a_kg, &a_kds, &a_ctl, &a_slabs };
-		void	   *args_pack[] = { &a_kg, &a_kds, &a_ctl, &a_pack, &a_slabs };
-		void	   *args_plook[] = { &a_kg, &a_kds, &a_jmap, &a_ctl, &a_pack, &a_slabs };
-		void	   *args_gen[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_ctl, &a_slabs };
-		void	   *args_join[] = { &a_kg, &a_res, &a_kds, &a_jmap, &a_ctl, &a_slabs };
-		void	   *args_look[] = { &a_kg, &a_kds, &a_jmap, &a_ctl, &a_slabs };
-		void	   *args_mrg[] = { &a_kg, &a_ctl, &a_slabs, &a_table };
-		void	  **fold_args = (packed ? (use_lookup ? args_plook : args_pack)
-								 : use_lookup ? args_look : use_joined ? args_join
-								 : use_column ? args_col : args_gen);
-		unsigned	fold_block = (use_reg ? 256 : (unsigned)sess->block);
-		unsigned	fold_lds = (unsigned)(packed ? packed->lds_bytes : sess->lds_bytes);
-		if (ext_launch)
-			REQ_CHECK(hipExtModuleLaunchKernel(fn, lctl.nslabs * fold_block, 1, 1, fold_block, 1, 1, fold_lds,
-											   task->stream, fold_args, nullptr, ev_fold_begin, ev_fold_done, 0),
-					  "launch gpupreagg reduction");
-		else
-			REQ_CHECK(hipModuleLaunchKernel(fn, lctl.nslabs, 1, 1, fold_block, 1, 1, fold_lds, task->stream,
-											fold_args, nullptr),
-					  "launch gpupreagg reduction");
-		if (packed)
-			task->pfm.num_kern_prep++;			/* (reported: this request took the packed path) */
-		hipEvent_t fold_done = ev_fold_done;
-		if (!ext_launch && (task->pfm.enabled || piped))
-		{
-			fold_done = task_event(task);				/* ev[2] (piped: ev[3]): main kernel done */
-			task->has_ev_proj = !piped;
-		}
-		if (piped)
-		{
-			/* the merge stream takes over: behind this fold and behind the previous merge */
-			if (!fold_done)
-			{
-				task_fail(task, StromError_HipInternal);
-				return;
-			}
-			REQ_CHECK(hipStreamWaitEvent(s_mrg, fold_done, 0), "merge waits for the fold");
-		}
-		if (sess->merge_ev_used[turn ^ 1])
-			REQ_CHECK(hipStreamWaitEvent(s_mrg, sess->merge_ev[turn ^ 1], 0), "merge waits for the previous merge");
-		/* the merge kernel lays 256 threads out as GL group lanes x stripes
-		 * over the slabs (strom_gpupreagg.h) */
-		unsigned ws = 1, per_split = lctl.nslabs / lctl.nsplits;
-		while (ws < 64 && ws * 8 < per_split)
-			ws <<= 1;
-		if (lctl.merge_ws != 0)
-			ws = lctl.merge_ws;
-		unsigned gl = 256 / ws;
-		unsigned mgrid = std::min<unsigned>((lctl.ngroups + gl - 1) / gl,
-											(unsigned)dev->prop.multiProcessorCount * 8);
-		/* the slab check: numeric sums; integer sums whose chunk totals the range proof may
-		 * not cover (tier 2: the kernel leaves at once when it does) */
-		if (sess->numeric_aggs || checked ||
-			(sess->nintsums > 0 && (sess->sums_measured || sess->static_magbits > 31)))
-		{
-			/* numeric sums may leave the 64-bit form while slabs are added up: find
-			 * out BEFORE the table takes any of it (gpupreagg_dense_merge_body<CHECK>) */
-			int		e3 = 0;
-			hipFunction_t fn_check = prog->get_function(dev, "gpupreagg_dense_merge_check", &e3);
-			if (!fn_check)
-			{
-				task_fail(task, e3);
-				return;
-			}
-			REQ_CHECK(hipModuleLaunchKernel(fn_check, std::max(1u, mgrid), 1, 1, 256, 1, 1, 0,
-											s_mrg, args_mrg, nullptr),
-					  "launch gpupreagg merge check");
-			task->pfm.num_kern_exec++;
-		}
-		REQ_CHECK(hipModuleLaunchKernel(fn_merge, std::max(1u, mgrid), 1, 1, 256, 1, 1, 0,
-										s_mrg, args_mrg, nullptr),
-				  "launch gpupreagg merge");
-		task->pfm.num_kern_exec += 2;
-		REQ_CHECK(hipEventRecord(sess->merge_ev[turn], s_mrg), "mark the merge");
-		sess->merge_ev_used[turn] = true;
-	}
-	task_event(task, s_mrg);							/* ev[2] (+1 with the fold event; piped: ev[4]) */
-	char   *stage_status = stage + send_len;
-	REQ_CHECK(hipMemcpyAsync(stage_status, d_kg + offsetof(kern_gpupreagg, status), sizeof(cl_int),
-							 hipMemcpyDeviceToHost, s_mrg),
-			  "recv status");
-	task->pfm.num_dma_recv++;
-	task->pfm.bytes_dma_recv += sizeof(cl_int);
-	task_event(task, s_mrg);							/* ev[3] (+1; piped: ev[5]) */
-	task->ev_preagg_piped = piped;
+	if (!queue_fold_and_merge(task, req, prog, checked, plan, sent, d_jmap, piped, s_in, s_mrg))
+		return;
 	if (checked)
 		sess->checked_folds++;
+	char   *stage_status = sent.stage + sent.send_len;
 	task->finish = [stage_status, req, checked](strom_task_impl *t)
 	{
 		cl_int status;
@@ -1144,26 +1256,14 @@ gpupreagg_launch(strom_task_impl *task, preagg_request req, bool checked = false
 			 */
 			t->retry = [t, req]()
 			{
-				if (req.star)
+				preagg_request again = req;
+				again.prog = checked_program(req);
+				if (!again.prog)
 				{
-					/* the star kernels live in the mapping's own program: its checked build */
-					preagg_request again = req;
-					again.prog = star_mapping_program(req.sess, req.star_defs, true);
-					if (!again.prog)
-					{
-						task_fail(t, StromError_OutOfMemory);
-						return;
-					}
-					program_run_or_park(again.prog, [t, again]() { gpupreagg_launch(t, again, true); });
+					task_fail(t, StromError_OutOfMemory);
 					return;
 				}
-				int		rc = ensure_checked_program(req.sess);
-				if (rc != 0)
-				{
-					task_fail(t, rc);
-					return;
-				}
-				program_run_or_park(req.sess->prog_checked, [t, req]() { gpupreagg_launch(t, req, true); });
+				program_run_or_park(again.prog, [t, again]() { gpupreagg_launch(t, again, true); });
 			};
 			return;
 		}
@@ -1524,23 +1624,6 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			return;
 		}
 	}
-	size_t	kg_len = STROMALIGN(offsetof(kern_gpupreagg, kparams) + sess->kparams.size());
-	char   *stage = dev->pinned.alloc();
-	char   *d_kg = (char *)dev->pool.alloc(kg_len);
-	if (!stage || !d_kg || kg_len + 64 > PinnedPool::BLOCK)
-	{
-		if (stage) dev->pinned.release(stage);
-		if (d_kg) dev->pool.release(d_kg);
-		task_fail(task, StromError_OutOfMemory);
-		return;
-	}
-	task->pinned_blocks.push_back(stage);
-	task->main_devptr = d_kg;
-	memset(stage, 0, kg_len);
-	memcpy(stage + offsetof(kern_gpupreagg, kparams), sess->kparams.data(), sess->kparams.size());
-	/* integer sums never wrap (strom_gpupreagg.h): rows of the request, what is known about
-	 * the inputs before the check pass measures the rest */
-	kern_gpupreagg_set_chunk_words((kern_gpupreagg *)stage, req.nrows, sess->static_magbits, 0, false);
 	/* the fold's turn (gpupreagg_hash_sum_account): parity; 4 = second attempt, after the
 	 * bound was measured; relaunches for deferred rows add 2 */
 	/* (bit 2 -- "a failed proof is final: CpuReCheck" -- is no longer asked for: the host sends an
@@ -1559,48 +1642,14 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			return;
 		}
 	}
-
-	task_event(task);									/* ev[0] */
-	REQ_CHECK(hipMemcpyAsync(d_kg, stage, kg_len, hipMemcpyHostToDevice, task->stream),
-			  "send kern_gpupreagg");
-	task->pfm.num_dma_send++;
-	task->pfm.bytes_dma_send += kg_len;
-	const void *d_kds;
-	if (req.kds_dev)
-		d_kds = req.kds_dev->devptr;
-	else
-	{
-		size_t	kds_len = req.kds->length;
-		if (req.kds->format == KDS_FORMAT_ROW)
-			kds_len = KERN_DATA_STORE_ROWBLOCK_OFFSET(req.kds) + (size_t)BLCKSZ * req.kds->nblocks;
-		void   *p = dev->pool.alloc(kds_len);
-		if (!p)
-		{
-			task_fail(task, StromError_OutOfMemory);
-			return;
-		}
-		task->devbufs.push_back(p);
-		REQ_CHECK(hipMemcpyAsync(p, req.kds, kds_len, hipMemcpyHostToDevice, task->stream),
-				  "send kern_data_store");
-		task->pfm.num_dma_send++;
-		task->pfm.bytes_dma_send += kds_len;
-		d_kds = p;
-	}
-	const void *d_rowmap = (req.rowmap_dev ? req.rowmap_dev->devptr : nullptr);
-	if (!req.rowmap_dev && req.krowmap)
-	{
-		size_t	len = offsetof(kern_row_map, rindex) + sizeof(cl_int) * (size_t)req.krowmap->nvalids;
-		void   *p = dev->pool.alloc(len);
-		if (!p)
-		{
-			task_fail(task, StromError_OutOfMemory);
-			return;
-		}
-		task->devbufs.push_back(p);
-		REQ_CHECK(hipMemcpyAsync(p, req.krowmap, len, hipMemcpyHostToDevice, task->stream),
-				  "send kern_row_map");
-		d_rowmap = p;
-	}
+	/* integer sums never wrap (strom_gpupreagg.h): rows of the request, what is known about
+	 * the inputs before the check pass measures the rest */
+	sent_request sent;
+	if (!send_request(task, req, task->stream, sess->static_magbits, 0, false, nullptr, &sent))	/* ev[0] */
+		return;
+	char	   *stage = sent.stage, *d_kg = sent.d_kg;
+	const size_t kg_len = sent.kg_len;
+	const void *d_kds = sent.d_kds, *d_rowmap = sent.d_rowmap;
 	task_event(task);									/* ev[1] */
 	/*
 	 * More groups than the hash roles' LDS tables take together (or than a few roles, each a
@@ -2413,174 +2462,271 @@ strom_submit_gpupreagg_mapped(strom_gpupreagg *sess, strom_dstore *kds_dev, stro
 }
 
 
+namespace {
+
 /*
- * fold the rows a finished GpuHashJoin produced, straight from its result
- * pairs (gpupreagg_dense_joined): see strom_hip.h
+ * the wanted columns of relation 'depth' (1-based) as hashjoin_table_dimrecs takes them: cols[] / lens[] /
+ * ints[] (may take the narrow form: not a float, not a numeric image), which[] the virtual column each one
+ * serves.  Returns their number, -1 for more than HASHJOIN_DIMREC_MAXCOLS.  Pure: no device, no session.
+ */
+int
+collect_relation_columns(int depth, int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+						 const int32_t *type_oids, int *cols, int *lens, int *ints, int *which, uint64_t *p_mask)
+{
+	int		n = 0;
+	*p_mask = 0;
+	for (int i = 0; i < ncols; i++)
+	{
+		if (src_depth[i] != depth)
+			continue;
+		if (n == HASHJOIN_DIMREC_MAXCOLS)
+			return -1;
+		int		oid = (type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
+		cols[n] = src_colidx[i];
+		lens[n] = type_length(oid);
+		ints[n] = !(type_is_float(oid) || oid == STROM_NUMERICOID);
+		which[n++] = i;
+		*p_mask |= ((uint64_t)1 << i);
+	}
+	return n;
+}
+
+/*
+ * One mapping builder for strom_submit_gpupreagg_joined, _lookup and _lookup_star: checks the arguments,
+ * asks every table what it is, downloads the outer chunk's head for its column widths, has every relation's
+ * slot records made and describes the result in *m.  Returns 0, or the code to refuse the request with.
+ * The entry points answer some faults with different codes and in a different order; callers may rely on
+ * either, so each difference is kept and marked where the code branches on the entry: (1) to (4) below.
+ */
+int
+build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jtask,
+				   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
+				   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
+				   fold_mapping *m)
+{
+	const bool	star = (entry == PREAGG_STAR);
+
+	if (!sess || sess->hashed || !sess->has_domain || (entry == PREAGG_JOINED && !jtask) || !tbls || !outer ||
+		ntbls < 1 || ntbls > GPUPREAGG_STAR_MAXRELS ||
+		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids)
+		return StromError_BadRequestMessage;
+	for (int r = 0; r < ntbls; r++)
+		if (!tbls[r])
+			return StromError_BadRequestMessage;
+	if (jtask)
+		task_wait_completed(jtask);
+	/* needs: (joined) a finished join with STROM_RESULTS_ON_DEVICE; per table one inner relation with a DIRECT
+	 * index and unique keys, joined on a plain outer column; a resident COLUMN chunk; all on the session's device */
+	int			outer_ncols = (int)outer->head.ncols;
+	bool		ok = (!jtask || (jtask->res_is_join && jtask->keep_main && jtask->errcode == 0 && jtask->main_devptr));
+	ok = ok && outer->head.format == KDS_FORMAT_COLUMN && outer->dindex == sess->dev->dindex;
+	m->ncols = ncols;
+	m->nrels = ntbls;
+	for (int r = 0; ok && r < ntbls; r++)
+	{
+		int		key_attno = 0, tbl_dindex = -1, has_outer_qual = 0;
+		ok = (hashjoin_table_direct_info(tbls[r], &m->key_min[r], &m->nslots[r], &key_attno,
+										 &tbl_dindex, &has_outer_qual) == 0 &&
+			  /* a lookup runs the aggregate program only: a WHERE that lives in the join
+			   * program would silently not be applied */
+			  !(entry != PREAGG_JOINED && has_outer_qual) &&
+			  key_attno >= 1 && key_attno <= outer_ncols && tbl_dindex == sess->dev->dindex);
+		m->key_col[r] = key_attno - 1;
+	}
+	if (!ok)
+		return ((jtask && jtask->errcode) ? jtask->errcode : StromError_BadRequestMessage);
+	/* (1) the star refuses a depth outside 0 .. ntbls and ANY negative column index up front, as a
+	 * BadRequest; the one-table calls meet them column by column below, where a negative index of an
+	 * OUTER column is a DataStoreCorruption */
+	for (int i = 0; star && i < ncols; i++)
+		if (src_depth[i] < 0 || src_depth[i] > ntbls || src_colidx[i] < 0)
+			return StromError_BadRequestMessage;
+	(void)hipSetDevice(sess->dev->hip_id);
+	/* the outer chunk's column widths */
+	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
+	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_BadRequestMessage;
+	const kern_data_store *oh = (const kern_data_store *)ohead.data();
+	/* (these kernels stream the outer columns: a text variable must be one of them) */
+	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
+		return StromError_BadRequestMessage;
+	/* (2) the width of a join key: 4 or 8 bytes for a lookup (BadRequest), 1, 2, 4 or 8 for result
+	 * pairs (DataStoreCorruption); the star looks BEFORE the columns, the one-table calls AFTER */
+	auto key_widths = [&]() -> int {
+		for (int r = 0; r < ntbls; r++)
+		{
+			int		len = m->key_attlen[r] = oh->colmeta[m->key_col[r]].attlen;
+			if (!(len == 4 || len == 8 || (entry == PREAGG_JOINED && (len == 1 || len == 2))))
+				return (entry == PREAGG_JOINED ? StromError_DataStoreCorruption : StromError_BadRequestMessage);
+		}
+		return 0;
+	};
+	int			rc = (star ? key_widths() : 0);
+	if (rc != 0)
+		return rc;
+	for (int i = 0; i < ncols; i++)
+	{
+		memset(&m->c[i], 0, sizeof(m->c[i]));
+		m->c[i].depth = src_depth[i];
+		m->c[i].col = src_colidx[i];
+		if (src_depth[i] == 0)
+		{
+			/* a text / character(n) column is an outer column's offset array: attlen -1.
+			 * (3) the one-table calls know the type by |oid|, the star by the oid as given: under
+			 * a negative oid it takes text for an 8-byte value, and refuses */
+			int		oid = (star ? type_oids[i] : type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
+			int		attlen = ((oid == STROM_TEXTOID || oid == STROM_BPCHARNOID) ? -1 : type_length(oid));
+			if (src_colidx[i] < 0 || src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen)
+				return StromError_DataStoreCorruption;
+		}
+		else if (src_depth[i] < 1 || src_depth[i] > ntbls || src_colidx[i] < 0)
+			return StromError_BadRequestMessage;	/* (an inner column itself: the build kernel checks it) */
+	}
+	rc = (star ? 0 : key_widths());
+	if (rc != 0)
+		return rc;
+	for (int r = 0; r < ntbls; r++)
+	{
+		/* one packed record per slot: presence, NULL bits and the wanted columns of relation r + 1 */
+		int			cols[HASHJOIN_DIMREC_MAXCOLS], lens[HASHJOIN_DIMREC_MAXCOLS];
+		int			which[HASHJOIN_DIMREC_MAXCOLS], ints[HASHJOIN_DIMREC_MAXCOLS];
+		unsigned	offs[HASHJOIN_DIMREC_MAXCOLS], reclen = 0;
+		void	   *recs = nullptr;
+		dimrec_narrow nw;
+		int			n = collect_relation_columns(r + 1, ncols, src_depth, src_colidx, type_oids,
+												 cols, lens, ints, which, &m->inner_mask[r]);
+		if (n < 0)
+			return StromError_BadRequestMessage;
+		/* (4) the lookup kernels also read the narrow form (2 / 4 bytes per slot: more of the table
+		 * stays in L2 while the fact columns stream past); the result pairs' kernel does not */
+		rc = hashjoin_table_dimrecs(tbls[r], n, cols, lens, offs, &recs, &reclen, ints,
+									entry == PREAGG_JOINED ? nullptr : &nw);
+		if (rc != 0)
+			return rc;
+		bool		narrow = (entry != PREAGG_JOINED && nw.spec.reclen != 0);
+		m->recs[r] = (cl_ulong)(uintptr_t)(narrow ? nw.recs : recs);
+		m->reclen[r] = (narrow ? nw.spec.reclen : reclen);
+		m->narrow[r] = (narrow ? 1 : 0);
+		for (int k = 0; k < n; k++)
+		{
+			auto   &c = m->c[which[k]];
+			c.recoff = (narrow ? 0 : offs[k]);		/* byte offset in the record */
+			c.nullbit = 1 + k;						/* bit in the flags word */
+			if (narrow)
+			{
+				c.nshift = nw.spec.shift[k];
+				c.nmask = nw.spec.mask[k];
+				c.nmin = nw.spec.vmin[k];
+			}
+		}
+	}
+	return 0;
+}
+
+/* the mapping as gpupreagg_dense_joined / _lookup read it (one relation) */
+std::shared_ptr<std::vector<char>>
+write_joined_map(const fold_mapping &m)
+{
+	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_joined_map), 0);
+	gpupreagg_joined_map *jm = (gpupreagg_joined_map *)img->data();
+	jm->ncols = m.ncols;
+	jm->key_col = m.key_col[0];
+	jm->key_attlen = m.key_attlen[0];
+	jm->nslots = m.nslots[0];
+	jm->key_min = m.key_min[0];
+	jm->recs = m.recs[0];
+	jm->reclen = m.reclen[0];
+	jm->narrow = m.narrow[0];
+	for (int i = 0; i < m.ncols; i++)
+	{
+		jm->c[i].depth = m.c[i].depth;
+		jm->c[i].col = m.c[i].col;
+		jm->c[i].dimvalues = m.c[i].recoff;
+		jm->c[i].dimisnull = m.c[i].nullbit;
+		jm->nshift[i] = m.c[i].nshift;
+		jm->nmask[i] = m.c[i].nmask;
+		jm->nmin[i] = m.c[i].nmin;
+	}
+	return img;
+}
+
+/* ... and as gpupreagg_dense_lookup_star / _packed_lookup_star read it */
+std::shared_ptr<std::vector<char>>
+write_star_map(const fold_mapping &m)
+{
+	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_star_map), 0);
+	gpupreagg_star_map *sm = (gpupreagg_star_map *)img->data();
+	sm->ncols = m.ncols;
+	sm->nrels = m.nrels;
+	for (int r = 0; r < m.nrels; r++)
+	{
+		sm->rel[r].key_col = m.key_col[r];
+		sm->rel[r].key_attlen = m.key_attlen[r];
+		sm->rel[r].nslots = m.nslots[r];
+		sm->rel[r].reclen = m.reclen[r];
+		sm->rel[r].key_min = m.key_min[r];
+		sm->rel[r].recs = m.recs[r];
+		sm->rel[r].narrow = m.narrow[r];
+	}
+	memcpy(sm->c, m.c, sizeof(sm->c[0]) * m.ncols);
+	return img;
+}
+
+}	/* namespace */
+
+/*
+ * The three fused folds (strom_hip.h): the rows a finished GpuHashJoin produced, straight from its result
+ * pairs (gpupreagg_dense_joined); the join as a lookup inside the aggregate's own pass over the outer chunk,
+ * no join request at all (gpupreagg_dense_lookup); a star of such lookups, one table per relation
+ * (gpupreagg_dense_lookup_star)
  */
 static strom_task *
-submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool lookup,
-						   strom_hashjoin_table *tbl, strom_dstore *outer,
-						   int ncols, const int32_t *src_depth, const int32_t *src_colidx,
-						   const int32_t *type_oids,
-						   strom_done_cb done, void *arg, int *p_errcode)
+submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *join_handle,
+					   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
+					   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
+					   strom_done_cb done, void *arg, int *p_errcode)
 {
 	STROM_ABI_TRY
 	int		dummy;
 	if (!p_errcode)
 		p_errcode = &dummy;
-	*p_errcode = 0;
 	strom_task_impl *jtask = static_cast<strom_task_impl *>(join_handle);
-	if (!sess || sess->hashed || !sess->has_domain || (!lookup && !jtask) || !tbl || !outer ||
-		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids)
-	{
-		*p_errcode = StromError_BadRequestMessage;
+	fold_mapping m;
+	preagg_request req;
+	*p_errcode = build_fold_mapping(sess, entry, jtask, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids, &m);
+	if (*p_errcode != 0)
 		return nullptr;
-	}
-	if (jtask)
-		task_wait_completed(jtask);
-	cl_long	key_min = 0;
-	cl_uint	nslots = 0;
-	int		key_attno = 0, tbl_dindex = -1, has_outer_qual = 0;
-	if ((jtask && (!jtask->res_is_join || !jtask->keep_main || jtask->errcode != 0 || !jtask->main_devptr)) ||
-		hashjoin_table_direct_info(tbl, &key_min, &nslots, &key_attno, &tbl_dindex, &has_outer_qual) != 0 ||
-		/* lookup mode runs the aggregate program only: a WHERE that lives in the
-		 * join program would silently not be applied */
-		(lookup && has_outer_qual) ||
-		key_attno < 1 || outer->head.format != KDS_FORMAT_COLUMN ||
-		outer->dindex != sess->dev->dindex || tbl_dindex != sess->dev->dindex)
+	req.sess = sess;
+	req.kds_dev = outer;
+	req.format = KDS_FORMAT_COLUMN;
+	req.nrows = outer->head.nitems;
+	req.kind = entry;
+	if (entry == PREAGG_STAR)
 	{
-		/* needs: a finished join with STROM_RESULTS_ON_DEVICE, one inner relation
-		 * with a DIRECT index and unique keys, joined on a plain outer column,
-		 * over a resident COLUMN chunk */
-		*p_errcode = ((jtask && jtask->errcode) ? jtask->errcode : StromError_BadRequestMessage);
-		return nullptr;
-	}
-	(void)hipSetDevice(sess->dev->hip_id);
-	/* the outer chunk's column widths */
-	int		outer_ncols = (int)outer->head.ncols;
-	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
-	if (key_attno > outer_ncols ||
-		hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
-	{
-		*p_errcode = StromError_BadRequestMessage;
-		return nullptr;
-	}
-	const kern_data_store *oh = (const kern_data_store *)ohead.data();
-	/* (these kernels stream the outer columns: a text variable must be one of them) */
-	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
-	{
-		*p_errcode = StromError_BadRequestMessage;
-		return nullptr;
-	}
-	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_joined_map), 0);
-	gpupreagg_joined_map *jm = (gpupreagg_joined_map *)img->data();
-	jm->ncols = ncols;
-	jm->key_col = key_attno - 1;
-	jm->key_attlen = oh->colmeta[key_attno - 1].attlen;
-	jm->nslots = nslots;
-	jm->key_min = key_min;
-	for (int i = 0; i < ncols; i++)
-	{
-		int		attlen;
-		switch (type_oids[i] < 0 ? -type_oids[i] : type_oids[i])
-		{
-			case STROM_BOOLOID: case STROM_BPCHAROID:	attlen = 1; break;
-			case STROM_INT2OID:							attlen = 2; break;
-			case STROM_INT4OID: case STROM_FLOAT4OID: case STROM_DATEOID:	attlen = 4; break;
-			case STROM_TEXTOID: case STROM_BPCHARNOID:	attlen = -1; break;		/* (outer columns only) */
-			default:									attlen = 8; break;
-		}
-		jm->c[i].depth = src_depth[i];
-		jm->c[i].col = src_colidx[i];
-		if (src_depth[i] == 0)
-		{
-			if (src_colidx[i] < 0 || src_colidx[i] >= outer_ncols ||
-				oh->colmeta[src_colidx[i]].attlen != attlen)
-			{
-				*p_errcode = StromError_DataStoreCorruption;
-				return nullptr;
-			}
-		}
-		else if (src_depth[i] == 1 && src_colidx[i] >= 0)
-			;						/* packed slot records, below (the build kernel checks the column) */
-		else
+		/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
+		 * all relations: no define block -- the kernel keeps a row's records in registers) */
+		req.star_defs = star_mapping_defines(ntbls, m.key_attlen, m.reclen, m.narrow, m.inner_mask);
+		if (req.star_defs.empty())
 		{
 			*p_errcode = StromError_BadRequestMessage;
 			return nullptr;
 		}
-	}
-	if (!(jm->key_attlen == 1 || jm->key_attlen == 2 || jm->key_attlen == 4 || jm->key_attlen == 8) ||
-		(lookup && !(jm->key_attlen == 4 || jm->key_attlen == 8)))
-	{
-		*p_errcode = (lookup ? StromError_BadRequestMessage : StromError_DataStoreCorruption);
-		return nullptr;
-	}
-	{
-		/* one packed record per slot: presence, NULL bits and the wanted inner columns */
-		const int MAXCOLS = HASHJOIN_DIMREC_MAXCOLS;
-		int		cols[MAXCOLS], lens[MAXCOLS], which[MAXCOLS], ints[MAXCOLS], n = 0;
-		unsigned offs[MAXCOLS], reclen = 0;
-		void   *recs = nullptr;
-		dimrec_narrow nw;
-		for (int i = 0; i < ncols; i++)
+		req.prog = star_mapping_program(sess, req.star_defs);
+		if (!req.prog)
 		{
-			if (src_depth[i] != 1)
-				continue;
-			if (n == MAXCOLS)
-			{
-				*p_errcode = StromError_BadRequestMessage;
-				return nullptr;
-			}
-			int		oid = (type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
-			cols[n] = src_colidx[i];
-			lens[n] = ((oid == STROM_BOOLOID || oid == STROM_BPCHAROID) ? 1 : oid == STROM_INT2OID ? 2
-					   : (oid == STROM_INT4OID || oid == STROM_FLOAT4OID || oid == STROM_DATEOID) ? 4 : 8);
-			ints[n] = !(oid == STROM_FLOAT4OID || oid == STROM_FLOAT8OID || oid == STROM_NUMERICOID);
-			which[n++] = i;
-		}
-		/* the lookup kernel also reads the narrow form (2 / 4 bytes per slot: more of the table
-		 * stays in L2 while the fact columns stream past) */
-		int		rc = hashjoin_table_dimrecs(tbl, n, cols, lens, offs, &recs, &reclen,
-											ints, lookup ? &nw : nullptr);
-		if (rc != 0)
-		{
-			*p_errcode = rc;
+			*p_errcode = StromError_OutOfMemory;
 			return nullptr;
 		}
-		for (int k = 0; k < n; k++)
-		{
-			jm->c[which[k]].dimvalues = offs[k];		/* byte offset in the record */
-			jm->c[which[k]].dimisnull = 1 + k;			/* bit in the flags word */
-		}
-		jm->recs = (cl_ulong)(uintptr_t)recs;
-		jm->reclen = reclen;
-		if (lookup && nw.spec.reclen != 0)
-		{
-			jm->recs = (cl_ulong)(uintptr_t)nw.recs;
-			jm->reclen = nw.spec.reclen;
-			jm->narrow = 1;
-			for (int k = 0; k < n; k++)
-			{
-				jm->c[which[k]].dimvalues = 0;
-				jm->nshift[which[k]] = nw.spec.shift[k];
-				jm->nmask[which[k]] = nw.spec.mask[k];
-				jm->nmin[which[k]] = nw.spec.vmin[k];
-			}
-		}
+		req.map = write_star_map(m);
 	}
-	preagg_request req;
-	req.sess = sess;
-	req.kds = nullptr;
-	req.kds_dev = outer;
-	req.krowmap = nullptr;
-	req.rowmap_dev = nullptr;
-	req.format = KDS_FORMAT_COLUMN;
-	req.joined_map = img;
-	req.lookup = lookup;
-	if (lookup)
-		req.nrows = outer->head.nitems;
+	else if (entry == PREAGG_LOOKUP)
+	{
+		req.prog = lookup_mapping_program(sess, m);
+		req.map = write_joined_map(m);
+	}
 	else
 	{
+		req.map = write_joined_map(m);
 		req.nrows = jtask->res_nitems;
 		req.joined_results = (const char *)jtask->main_devptr + jtask->res_offset;
 		/* the result pairs now belong to this request: the join task can be
@@ -2589,8 +2735,6 @@ submit_gpupreagg_over_join(strom_gpupreagg *sess, strom_task *join_handle, bool 
 		jtask->main_devptr = nullptr;
 		jtask->keep_main = false;
 	}
-	if (lookup)
-		req.prog = lookup_mapping_program(sess, jm);
 	sess->nfolds++;
 	strom_task_impl *task = task_create(sess->dev, done, arg);
 	program_run_or_park(req.prog ? req.prog : sess->prog, [task, req]() { gpupreagg_launch(task, req); });
@@ -2605,14 +2749,10 @@ strom_submit_gpupreagg_joined(strom_gpupreagg *sess, strom_task *join_handle,
 							  const int32_t *type_oids,
 							  strom_done_cb done, void *arg, int *p_errcode)
 {
-	return submit_gpupreagg_over_join(sess, join_handle, false, tbl, outer, ncols, src_depth, src_colidx,
-									  type_oids, done, arg, p_errcode);
+	return submit_gpupreagg_fused(sess, PREAGG_JOINED, join_handle, &tbl, 1, outer, ncols, src_depth, src_colidx,
+								  type_oids, done, arg, p_errcode);
 }
 
-/*
- * the join as a lookup inside the aggregate's own pass over the outer chunk
- * (gpupreagg_dense_lookup): no join request at all
- */
 extern "C" strom_task *
 strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
 							  strom_hashjoin_table *tbl, strom_dstore *outer,
@@ -2620,8 +2760,8 @@ strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
 							  const int32_t *type_oids,
 							  strom_done_cb done, void *arg, int *p_errcode)
 {
-	return submit_gpupreagg_over_join(sess, nullptr, true, tbl, outer, ncols, src_depth, src_colidx,
-									  type_oids, done, arg, p_errcode);
+	return submit_gpupreagg_fused(sess, PREAGG_LOOKUP, nullptr, &tbl, 1, outer, ncols, src_depth, src_colidx,
+								  type_oids, done, arg, p_errcode);
 }
 
 extern "C" int
@@ -2636,11 +2776,6 @@ strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, const int3
 	return (int)defs.size();
 }
 
-/*
- * a star of lookups inside the aggregate's own pass (gpupreagg_dense_lookup_star): see strom_hip.h.
- * One table per relation: hashjoin_table_direct_info / hashjoin_table_dimrecs (the narrow records
- * and the per-table cache included) serve each relation as they serve the one-table call.
- */
 extern "C" strom_task *
 strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 								   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
@@ -2649,163 +2784,9 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 								   strom_done_cb done, void *arg, int *p_errcode)
 {
 	static_assert(STROM_LOOKUP_STAR_MAXRELS == GPUPREAGG_STAR_MAXRELS, "star relations");
-	if (ntbls == 1 && tbls)
-		return submit_gpupreagg_over_join(sess, nullptr, true, tbls[0], outer, ncols, src_depth, src_colidx,
-										  type_oids, done, arg, p_errcode);
-	STROM_ABI_TRY
-	int		dummy;
-	if (!p_errcode)
-		p_errcode = &dummy;
-	*p_errcode = StromError_BadRequestMessage;
-	if (!sess || sess->hashed || !sess->has_domain || !tbls || !outer ||
-		ntbls < 1 || ntbls > STROM_LOOKUP_STAR_MAXRELS ||
-		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids ||
-		outer->head.format != KDS_FORMAT_COLUMN ||
-		outer->dindex != sess->dev->dindex)
-		return nullptr;
-	auto	img = std::make_shared<std::vector<char>>(sizeof(gpupreagg_star_map), 0);
-	gpupreagg_star_map *sm = (gpupreagg_star_map *)img->data();
-	int		key_attno[STROM_LOOKUP_STAR_MAXRELS];
-	int		outer_ncols = (int)outer->head.ncols;
-
-	sm->ncols = ncols;
-	sm->nrels = ntbls;
-	for (int r = 0; r < ntbls; r++)
-	{
-		int		tbl_dindex = -1, has_outer_qual = 0;
-		if (!tbls[r] ||
-			hashjoin_table_direct_info(tbls[r], &sm->rel[r].key_min, &sm->rel[r].nslots, &key_attno[r],
-									   &tbl_dindex, &has_outer_qual) != 0 ||
-			/* only the aggregate program runs: a WHERE in a join program would not be applied */
-			has_outer_qual || key_attno[r] < 1 || key_attno[r] > outer_ncols ||
-			tbl_dindex != sess->dev->dindex)
-			return nullptr;
-		sm->rel[r].key_col = key_attno[r] - 1;
-	}
-	for (int i = 0; i < ncols; i++)
-		if (src_depth[i] < 0 || src_depth[i] > ntbls || src_colidx[i] < 0)
-			return nullptr;
-	(void)hipSetDevice(sess->dev->hip_id);
-	/* the outer chunk's column widths */
-	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
-	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
-		return nullptr;
-	const kern_data_store *oh = (const kern_data_store *)ohead.data();
-	/* (these kernels stream the outer columns: a text variable must be one of them) */
-	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
-		return nullptr;
-	auto attlen_of = [](int32_t type_oid) -> int {
-		switch (type_oid < 0 ? -type_oid : type_oid)
-		{
-			case STROM_BOOLOID: case STROM_BPCHAROID:	return 1;
-			case STROM_INT2OID:							return 2;
-			case STROM_INT4OID: case STROM_FLOAT4OID: case STROM_DATEOID:	return 4;
-			default:									return 8;
-		}
-	};
-	for (int r = 0; r < ntbls; r++)
-	{
-		sm->rel[r].key_attlen = oh->colmeta[key_attno[r] - 1].attlen;
-		if (!(sm->rel[r].key_attlen == 4 || sm->rel[r].key_attlen == 8))
-			return nullptr;
-	}
-	for (int i = 0; i < ncols; i++)
-	{
-		sm->c[i].depth = src_depth[i];
-		sm->c[i].col = src_colidx[i];
-		/* (a text / character(n) column is an outer column's offset array: attlen -1) */
-		bool	varlena = (type_oids[i] == STROM_TEXTOID || type_oids[i] == STROM_BPCHARNOID);
-		if (src_depth[i] == 0 &&
-			(src_colidx[i] >= outer_ncols ||
-			 oh->colmeta[src_colidx[i]].attlen != (varlena ? -1 : attlen_of(type_oids[i]))))
-		{
-			*p_errcode = StromError_DataStoreCorruption;
-			return nullptr;
-		}
-	}
-	int32_t		keylen[STROM_LOOKUP_STAR_MAXRELS], reclens[STROM_LOOKUP_STAR_MAXRELS], narrows[STROM_LOOKUP_STAR_MAXRELS];
-	uint64_t	masks[STROM_LOOKUP_STAR_MAXRELS];
-	for (int r = 0; r < ntbls; r++)
-	{
-		/* one packed record per slot: presence, NULL bits and the wanted columns of relation r + 1 */
-		const int MAXCOLS = HASHJOIN_DIMREC_MAXCOLS;
-		int		cols[MAXCOLS], lens[MAXCOLS], which[MAXCOLS], ints[MAXCOLS], n = 0;
-		unsigned offs[MAXCOLS], reclen = 0;
-		void   *recs = nullptr;
-		dimrec_narrow nw;
-
-		masks[r] = 0;
-		for (int i = 0; i < ncols; i++)
-		{
-			if (src_depth[i] != r + 1)
-				continue;
-			if (n == MAXCOLS)
-				return nullptr;
-			int		oid = (type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
-			cols[n] = src_colidx[i];
-			lens[n] = attlen_of(type_oids[i]);
-			ints[n] = !(oid == STROM_FLOAT4OID || oid == STROM_FLOAT8OID || oid == STROM_NUMERICOID);
-			which[n++] = i;
-			masks[r] |= ((uint64_t)1 << i);
-		}
-		int		rc = hashjoin_table_dimrecs(tbls[r], n, cols, lens, offs, &recs, &reclen, ints, &nw);
-		if (rc != 0)
-		{
-			*p_errcode = rc;
-			return nullptr;
-		}
-		for (int k = 0; k < n; k++)
-		{
-			sm->c[which[k]].recoff = offs[k];
-			sm->c[which[k]].nullbit = 1 + k;
-		}
-		sm->rel[r].recs = (cl_ulong)(uintptr_t)recs;
-		sm->rel[r].reclen = reclen;
-		if (nw.spec.reclen != 0)
-		{
-			sm->rel[r].recs = (cl_ulong)(uintptr_t)nw.recs;
-			sm->rel[r].reclen = nw.spec.reclen;
-			sm->rel[r].narrow = 1;
-			for (int k = 0; k < n; k++)
-			{
-				sm->c[which[k]].recoff = 0;
-				sm->c[which[k]].nshift = nw.spec.shift[k];
-				sm->c[which[k]].nmask = nw.spec.mask[k];
-				sm->c[which[k]].nmin = nw.spec.vmin[k];
-			}
-		}
-		keylen[r] = sm->rel[r].key_attlen;
-		reclens[r] = (int32_t)sm->rel[r].reclen;
-		narrows[r] = (int32_t)sm->rel[r].narrow;
-	}
-	/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
-	 * all relations: no define block -- the kernel keeps a row's records in registers) */
-	preagg_request req;
-	req.star_defs = star_mapping_defines(ntbls, keylen, reclens, narrows, masks);
-	if (req.star_defs.empty())
-		return nullptr;
-	req.prog = star_mapping_program(sess, req.star_defs);
-	if (!req.prog)
-	{
-		*p_errcode = StromError_OutOfMemory;
-		return nullptr;
-	}
-	req.sess = sess;
-	req.kds = nullptr;
-	req.kds_dev = outer;
-	req.krowmap = nullptr;
-	req.rowmap_dev = nullptr;
-	req.format = KDS_FORMAT_COLUMN;
-	req.joined_map = img;
-	req.lookup = true;
-	req.star = true;
-	req.nrows = outer->head.nitems;
-	*p_errcode = 0;
-	sess->nfolds++;
-	strom_task_impl *task = task_create(sess->dev, done, arg);
-	program_run_or_park(req.prog, [task, req]() { gpupreagg_launch(task, req); });
-	return task;
-	STROM_ABI_CATCH(nullptr, p_errcode)
+	/* (one relation is the one-table call, its kernel and its error codes) */
+	return submit_gpupreagg_fused(sess, (ntbls == 1 && tbls) ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
+								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode);
 }
 
 /*
@@ -3362,8 +3343,6 @@ strom_gpupreagg_release(strom_gpupreagg *sess)
 			(void)hipEventDestroy(sess->merge_ev[b]);
 	if (sess->htab)
 		dev->pool.release(sess->htab);
-	if (sess->key_checked)
-		strom_put_devprog_key(sess->key_checked);
 	for (auto &kv : sess->lookup_programs)
 		strom_put_devprog_key(kv.second.first);
 	strom_put_devprog_key(sess->key);
@@ -4070,20 +4049,21 @@ chunk_domain(strom_devprog_key key, Program *prog, Device *dev,
 	if (kds_dev->head.format == KDS_FORMAT_COLUMN && !krowmap && !getenv("STROM_GPUPREAGG_NO_ZONE_DOMAIN"))
 	{
 		const char *lst = strstr(prog->source.c_str(), "#define GPUPREAGG_KEYCOLS_LIST(X)");
-		std::shared_ptr<std::vector<kern_coldir>> cd = dstore_coldir(kds_dev);
-		bool		ok = (lst != nullptr && cd != nullptr);
+		chunk_coldir dir;
+		chunk_coldir_of(nullptr, kds_dev, nullptr, &dir);
+		bool		ok = (lst != nullptr && dir.cd != nullptr);
 		const char *eol = (lst ? strchr(lst, '\n') : nullptr);
 		int			found = 0;
 		for (const char *p = (ok ? strstr(lst, " X(") : nullptr); ok && p && (!eol || p < eol); p = strstr(p + 1, " X("))
 		{
 			int		kidx = -1, attno = 0;
 			if (sscanf(p, " X(%d,%d)", &kidx, &attno) != 2 || kidx != found || kidx >= nkeys ||
-				attno < 1 || attno > (int)cd->size())
+				attno < 1 || attno > (int)dir.ncols)
 			{
 				ok = false;
 				break;
 			}
-			const kern_coldir &c = (*cd)[attno - 1];
+			const kern_coldir &c = dir.cd[attno - 1];
 			if (c.stat_flags & KDS_COLSTAT_ISFLOAT)
 				ok = false;
 			else if (!(c.stat_flags & KDS_COLSTAT_MINMAX))

@@ -89,6 +89,16 @@ def lookup_star_defines(relations):
     return buf.value.decode()
 
 
+def _column_mapping(columns):
+    """columns [(depth, attno, sqltype)] as join_to_column takes them -> the (src_depth, src_colidx,
+    type_oids) int32 arrays of the strom_submit_gpupreagg_joined / _lookup / _lookup_star calls"""
+    from .kds import column_type_oid
+    depth = np.array([d for d, _, _ in columns], dtype=np.int32)
+    colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
+    oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
+    return depth, colidx, oids
+
+
 class PartialRows(object):
     """decoded TUPSLOT result: one partial row per group"""
 
@@ -230,10 +240,7 @@ class GpuPreAgg(object):
         The join's device results pass to this request.  A text / character(n) variable of the
         program must be a column of 'chunk': mapped at depth 0, as "text" / "character", onto a
         varlena column (BadRequest otherwise; a dimension serves fixed-width columns only)."""
-        from .kds import column_type_oid
-        depth = np.array([d for d, _, _ in columns], dtype=np.int32)
-        colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
+        depth, colidx, oids = _column_mapping(columns)
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_joined(self.session, join_pending[0], join.table, chunk.handle,
                                                  len(columns), depth.ctypes.data, colidx.ctypes.data,
@@ -250,10 +257,7 @@ class GpuPreAgg(object):
         0, as "text" / "character", onto a varlena column of 'chunk' -- BadRequest otherwise, a
         dimension serves fixed-width columns only.  An unreadable (compressed / external) datum in
         a row that has a partner sends the chunk back (status 2, nothing folded)."""
-        from .kds import column_type_oid
-        depth = np.array([d for d, _, _ in columns], dtype=np.int32)
-        colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
+        depth, colidx, oids = _column_mapping(columns)
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_lookup(self.session, join.table, chunk.handle,
                                                  len(columns), depth.ctypes.data, colidx.ctypes.data,
@@ -268,10 +272,7 @@ class GpuPreAgg(object):
         it); columns as in join_to_column with depth 0 .. len(joins).  An inner join: a row is
         folded only if every relation has a partner.  Text / character(n) variables as in
         submit_lookup: fact columns only, mapped at depth 0 under their own type."""
-        from .kds import column_type_oid
-        depth = np.array([d for d, _, _ in columns], dtype=np.int32)
-        colidx = np.array([a - 1 for _, a, _ in columns], dtype=np.int32)
-        oids = np.array([column_type_oid(t) for _, _, t in columns], dtype=np.int32)
+        depth, colidx, oids = _column_mapping(columns)
         tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_lookup_star(self.session, tbls, len(joins), chunk.handle,

@@ -579,6 +579,51 @@ int			strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, cons
 												const int32_t *narrow, const uint64_t *inner_mask,
 												char *buf, size_t buflen);
 
+/*
+ * ... and a SNOWFLAKE: a relation keyed by ANOTHER RELATION's column ("lineitem -> orders ->
+ * customer", "fact -> product -> brand").  The fold kernels never decide a probe from another
+ * relation's record; they do not have to: the tables are DIRECT with unique keys, so a child
+ * relation is a function of its parent's slot, and the dimensions are joined to EACH OTHER once,
+ * at table time, into the parent's slot records (hashjoin_compose_dimrec_kernel).  What is left
+ * is the star of the tree's roots, each with composed records over its own slots -- one root is
+ * the one-table lookup (both forms of its mapping), 2 .. STROM_LOOKUP_STAR_MAXRELS roots are the
+ * star, with the star's own define block and programs.  Composed records are kept with the root
+ * table, per column set and per set of descendant tables, and freed with it.
+ * tbls[d - 1] is relation d as strom_submit_gpupreagg_lookup takes it; its program's outer key
+ * column is a column of the fact chunk where parent[d - 1] is 0, otherwise of relation
+ * parent[d - 1] < d (that program's outer relation), whose type link_type_oids[d - 1] names (int4,
+ * date or int8; ignored for a root).  src_depth[i] is 0 .. ntbls as in the star: any relation may
+ * serve columns, one that serves none is an existence filter.  An inner join: a row is folded
+ * only if every relation of the tree has a partner (a NULL link, a link outside the child's key
+ * range or in one of its holes: no partner).
+ * parent[] all zero is strom_submit_gpupreagg_lookup_star, ntbls == 1 strom_submit_gpupreagg_lookup:
+ * their code paths, their error codes.  BadRequest, and nothing is launched: a NULL argument, ntbls
+ * outside 1 .. STROM_LOOKUP_SNOWFLAKE_MAXRELS, parent[d - 1] outside 0 .. d - 1, more than
+ * STROM_LOOKUP_STAR_MAXRELS roots, a table that fails the one-table requirements or lives on
+ * another device, a link type that is not int4 / date / int8, a composed relation of more than 16
+ * columns at any step, with 2 roots and more a composed record longer than 16 bytes or records
+ * that total more than 32 bytes over all roots, a text variable not at depth 0, a hashed session,
+ * a session without a domain.  A link column the parent does not have, or of another width than
+ * its type says: DataStoreCorruption, like a served column.
+ */
+#define STROM_LOOKUP_SNOWFLAKE_MAXRELS 8    /* the join's own limit on inner relations */
+strom_task *strom_submit_gpupreagg_lookup_snowflake(strom_gpupreagg *sess,
+        strom_hashjoin_table *const *tbls, int ntbls,
+        const int32_t *parent,          /* [ntbls] 0: joined on a fact column; p in 1..d-1: on a column of relation p */
+        const int32_t *link_type_oids,  /* [ntbls] type of the parent's column that joins relation d (ignored where parent is 0) */
+        strom_dstore *outer, int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+        const int32_t *type_oids, strom_done_cb done, void *arg, int *p_errcode);
+/*
+ * Which star a snowflake flattens to (no device needed; the submit path uses it): the number of
+ * roots, or -1 for an invalid tree (ntbls, parent[] or a depth outside the ranges above, more
+ * than STROM_LOOKUP_STAR_MAXRELS roots).  root_of[d - 1]: the ordinal 1 .. of the root whose
+ * subtree holds relation d; col_root[i]: 0 for an outer column, else that ordinal for the
+ * relation that serves virtual column i.  Either may be NULL.
+ */
+int strom_gpupreagg_lookup_snowflake_roots(int ntbls, const int32_t *parent, int ncols, const int32_t *src_depth,
+                                           int32_t *root_of /* [ntbls] ordinal 1.. of each relation's root */,
+                                           int32_t *col_root /* [ncols] 0 or that ordinal */);
+
 /* ------------------------------------------------------------------ *
  * chained operators: device-resident row maps
  *

@@ -404,6 +404,31 @@ struct hashjoin_dimrec_narrow_spec {
 	cl_uint		mask[HASHJOIN_DIMREC_MAXCOLS];
 	cl_long		vmin[HASHJOIN_DIMREC_MAXCOLS];
 };
+/*
+ * a snowflake flattened at table time (hashjoin_compose_dimrec_kernel): the child relation's standard
+ * records joined into the parent's, over the PARENT's slots.  The parent's records hold the link
+ * column, the child's key; an output column is a parent's or a child's, copied with its NULL bit
+ * (output column i has bit 1 + i, as in every standard record).
+ */
+struct hashjoin_compose_spec {
+	cl_uint		ncols;				/* of the output */
+	cl_uint		reclen;
+	cl_uint		parent_reclen;
+	cl_uint		child_reclen;
+	cl_int		link_attlen;		/* 4 or 8 */
+	cl_uint		link_offset;		/* the link column in the parent's record ... */
+	cl_uint		link_nullbit;		/* ... and its bit in that record's flags word */
+	cl_uint		__pad;
+	struct {
+		cl_uint		from_child;		/* 0: the parent's record, 1: the child's */
+		cl_int		attlen;
+		cl_uint		src_offset;
+		cl_uint		src_nullbit;
+		cl_uint		offset;			/* of the value inside the output record */
+		cl_uint		__pad;
+	} c[HASHJOIN_DIMREC_MAXCOLS];
+};
+static_assert(sizeof(hashjoin_compose_spec) == 416, "hashjoin_compose_spec");
 static_assert(sizeof(hashjoin_dimrec_spec) == 264, "hashjoin_dimrec_spec");
 static_assert(sizeof(hashjoin_dimrec_range) == 320, "hashjoin_dimrec_range");
 static_assert(sizeof(hashjoin_dimrec_narrow_spec) == 264, "hashjoin_dimrec_narrow_spec");

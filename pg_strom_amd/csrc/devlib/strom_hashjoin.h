@@ -1492,6 +1492,135 @@ hashjoin_build_dimrec_kernel(const kern_multihash *kmhash, const hashjoin_index 
 }
 
 /* ====================================================================== *
+ * a SNOWFLAKE flattened at table time: relation c is keyed by a column x of
+ * relation p, not by a fact column.  Both tables are DIRECT with unique
+ * keys, so c's record is a function of p's slot: join the two once, into
+ * standard records over p's slots, and "fact JOIN p JOIN c" is a one-table
+ * lookup (the fold kernels never decide a probe from another relation's
+ * record: that would chain the relations' L2 round trips).
+ *
+ * A parent slot is present in the output if the parent is, x is not NULL,
+ * x - child key_min is a slot of the child (the fold kernels' rule) and the
+ * child's record is present; an absent slot is what
+ * hashjoin_build_dimrec_kernel writes for one.  The parent's records are
+ * read as a stream, the child's record is one random read of its length.
+ * ====================================================================== */
+
+/* a standard record's flags word and values: 8 / 16 bytes in one load, a longer record's flags word
+ * alone (its values are then read where they lie) */
+struct hashjoin_dimrec_words {
+	cl_ulong	lo, hi;
+};
+
+STROM_DEVICE hashjoin_dimrec_words
+hashjoin_dimrec_load(const char *rec, cl_uint reclen)
+{
+	hashjoin_dimrec_words r;
+	if (reclen == 8)
+	{
+		r.lo = *(const cl_ulong *)rec;
+		r.hi = 0;
+	}
+	else if (reclen == 16)
+	{
+		uint4	q = *(const uint4 *)rec;
+		r.lo = ((cl_ulong)q.y << 32) | q.x;
+		r.hi = ((cl_ulong)q.w << 32) | q.z;
+	}
+	else
+	{
+		r.lo = *(const cl_uint *)rec;
+		r.hi = 0;
+	}
+	return r;
+}
+
+/* the attlen bytes at 'offset' (naturally aligned: never across the two words), in the low bits */
+STROM_DEVICE cl_ulong
+hashjoin_dimrec_bits(const hashjoin_dimrec_words &r, const char *rec, cl_uint reclen, cl_uint offset, cl_int attlen)
+{
+	if (reclen <= 16)
+		return (offset < 8 ? r.lo : r.hi) >> ((offset & 7u) * 8u);
+	switch (attlen)
+	{
+		case 1:  return *(const cl_uchar *)(rec + offset);
+		case 2:  return *(const cl_ushort *)(rec + offset);
+		case 4:  return *(const cl_uint *)(rec + offset);
+		default: return *(const cl_ulong *)(rec + offset);
+	}
+}
+
+extern "C" __global__ void
+__launch_bounds__(256)
+hashjoin_compose_dimrec_kernel(const hashjoin_compose_spec *spec,
+							   const char *parent_recs, cl_uint parent_nslots,
+							   const char *child_recs, cl_long child_key_min, cl_uint child_nslots,
+							   char *recs)
+{
+	cl_uint		ncols = spec->ncols;
+	cl_uint		reclen = spec->reclen;
+	cl_uint		parent_reclen = spec->parent_reclen;
+	cl_uint		child_reclen = spec->child_reclen;
+	cl_int		link_attlen = spec->link_attlen;
+	cl_uint		link_offset = spec->link_offset;
+	cl_uint		link_nullbit = spec->link_nullbit;
+	cl_uint		absent = (2u << ncols) - 2u;		/* every NULL bit, bit 0 clear */
+
+	for (cl_uint s = blockIdx.x * blockDim.x + threadIdx.x; s < parent_nslots; s += gridDim.x * blockDim.x)
+	{
+		const char *prec = parent_recs + (size_t)parent_reclen * s;
+		const char *crec = child_recs;
+		char	   *rec = recs + (size_t)reclen * s;
+		hashjoin_dimrec_words pw = hashjoin_dimrec_load(prec, parent_reclen);
+		hashjoin_dimrec_words cw = { 0, 0 };
+		cl_uint		pflags = (cl_uint)pw.lo;
+		bool		present = ((pflags & 1u) != 0 && ((pflags >> link_nullbit) & 1u) == 0);
+
+		if (present)
+		{
+			cl_ulong	bits = hashjoin_dimrec_bits(pw, prec, parent_reclen, link_offset, link_attlen);
+			cl_long		x = (link_attlen == 4 ? (cl_long)(cl_int)(cl_uint)bits : (cl_long)bits);
+			cl_ulong	cslot = (cl_ulong)(x - child_key_min);
+
+			present = (cslot < (cl_ulong)child_nslots);
+			if (present)
+			{
+				crec = child_recs + (size_t)child_reclen * cslot;
+				cw = hashjoin_dimrec_load(crec, child_reclen);
+				present = (((cl_uint)cw.lo & 1u) != 0);
+			}
+		}
+		cl_uint		cflags = (cl_uint)cw.lo;
+		cl_uint		flags = (present ? 1u : absent);
+
+		for (cl_uint i = 0; i < ncols; i++)
+		{
+			cl_int		attlen = spec->c[i].attlen;
+			char	   *out = rec + spec->c[i].offset;
+			cl_ulong	v = 0;
+
+			if (present)
+			{
+				bool	from_child = (spec->c[i].from_child != 0);
+				cl_uint	src_offset = spec->c[i].src_offset;
+
+				v = (from_child ? hashjoin_dimrec_bits(cw, crec, child_reclen, src_offset, attlen)
+					 : hashjoin_dimrec_bits(pw, prec, parent_reclen, src_offset, attlen));
+				flags |= (((from_child ? cflags : pflags) >> spec->c[i].src_nullbit) & 1u) << (1 + i);
+			}
+			switch (attlen)
+			{
+				case 1: *(cl_uchar *)out = (cl_uchar)v; break;
+				case 2: *(cl_ushort *)out = (cl_ushort)v; break;
+				case 4: *(cl_uint *)out = (cl_uint)v; break;
+				default: *(cl_ulong *)out = v; break;
+			}
+		}
+		*(cl_uint *)rec = flags;
+	}
+}
+
+/* ====================================================================== *
  * NARROW slot records: the same information in 2 or 4 bytes per slot.
  *
  * A probe into the slot records is one random read; what it costs depends on

@@ -39,6 +39,18 @@ struct strom_hashjoin_table {
 	/* narrow form of a record set (same key), built on the first lookup that can take it;
 	 * reclen 0 = tried, does not fit */
 	std::map<std::string, dimrec_narrow> dimrecs_narrow;
+	/* a snowflake below this table flattened into its slot records (hashjoin_snowflake_dimrecs),
+	 * kept with the ROOT: key = the subtree as text, every descendant by its serial number (not
+	 * its address: a released table's is used again) */
+	uint64_t			serial = 0;
+	struct composed_dimrecs {
+		char			   *recs = nullptr;
+		hashjoin_dimrec_spec spec = {};			/* the composed records' layout: their columns are the served ones */
+		std::vector<int>	recpos;				/* served column k of the request -> its column in the record */
+		bool				narrow_tried = false;
+		dimrec_narrow		narrow;
+	};
+	std::map<std::string, composed_dimrecs> composed;
 };
 
 extern "C" strom_hashjoin_table *
@@ -107,6 +119,8 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 		return nullptr;
 	}
 	std::unique_ptr<strom_hashjoin_table> tbl(new strom_hashjoin_table());
+	static std::atomic<uint64_t> next_serial{1};
+	tbl->serial = next_serial++;
 	tbl->key = key;
 	tbl->prog = prog;
 	tbl->dev = dev;
@@ -278,6 +292,12 @@ strom_hashjoin_table_release(strom_hashjoin_table *tbl)
 	for (auto &kv : tbl->dimrecs_narrow)
 		if (kv.second.recs)
 			dev->pool.release(kv.second.recs);
+	for (auto &kv : tbl->composed)
+	{
+		dev->pool.release(kv.second.recs);
+		if (kv.second.narrow.recs)
+			dev->pool.release(kv.second.narrow.recs);
+	}
 	strom_put_devprog_key(tbl->key);
 	delete tbl;
 }
@@ -856,6 +876,130 @@ strom::hashjoin_table_dimcol(strom_hashjoin_table *tbl, int col, int attlen, voi
 	return 0;
 }
 
+namespace {
+
+/*
+ * the narrow form of standard slot records (spec, recs) over nslots slots, made by the table's
+ * program: ranges of the columns over the present, non-NULL values -> field widths; 1 + n flag
+ * bits + the fields must fit 16 or 32 bits.  spec.reclen 0 in the result: they do not.
+ */
+dimrec_narrow
+dimrecs_narrow_form(strom_hashjoin_table *tbl, const hashjoin_dimrec_spec &spec, const void *recs, cl_uint nslots)
+{
+	Device	   *dev = tbl->dev;
+	int			n = (int)spec.ncols;
+	hashjoin_dimrec_range rg;
+	dimrec_narrow	nw;
+	hashjoin_dimrec_narrow_spec &ns = nw.spec;
+	int			errcode = 0;
+	hipStream_t	stream = dev->streams[0];
+	(void)hipSetDevice(dev->hip_id);
+	hipFunction_t fn_mm = tbl->prog->get_function(dev, "hashjoin_dimrec_minmax_kernel", &errcode);
+	hipFunction_t fn_nw = tbl->prog->get_function(dev, "hashjoin_dimrec_narrow_kernel", &errcode);
+	char   *d_spec = (char *)dev->pool.alloc(sizeof(spec));
+	char   *d_rg = (char *)dev->pool.alloc(sizeof(rg));
+	char   *d_ns = (char *)dev->pool.alloc(sizeof(ns));
+	unsigned	grid = std::max(1u, std::min<unsigned>((nslots + 255) / 256,
+												   (unsigned)dev->prop.multiProcessorCount * 8));
+	memset(&rg, 0, sizeof(rg));
+	for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
+	{
+		rg.vmin[i] = INT64_MAX;
+		rg.vmax[i] = INT64_MIN;
+	}
+	bool	ok = (fn_mm && fn_nw && d_spec && d_rg && d_ns);
+	if (ok)
+	{
+		const void *a_spec = d_spec;
+		const void *a_recs = recs;
+		void	   *a_rg = d_rg;
+		void	   *args[] = { &a_spec, &a_recs, &nslots, &a_rg };
+		ok = (hipMemcpyAsync(d_spec, &spec, sizeof(spec), hipMemcpyHostToDevice, stream) == hipSuccess &&
+			  hipMemcpyAsync(d_rg, &rg, sizeof(rg), hipMemcpyHostToDevice, stream) == hipSuccess &&
+			  hipModuleLaunchKernel(fn_mm, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
+			  hipMemcpyAsync(&rg, d_rg, sizeof(rg), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+			  hipStreamSynchronize(stream) == hipSuccess);
+	}
+	unsigned	bits = 1 + (unsigned)n;
+	memset(&ns, 0, sizeof(ns));
+	for (int i = 0; ok && i < n; i++)
+	{
+		cl_ulong span = (rg.nvalues[i] ? (cl_ulong)rg.vmax[i] - (cl_ulong)rg.vmin[i] : 0);
+		unsigned w = 0;
+		while (w < 64 && (span >> w) != 0)
+			w++;
+		if (w > 31 || bits + w > 32)
+		{
+			ok = false;
+			break;
+		}
+		ns.shift[i] = bits;
+		ns.mask[i] = (w == 0 ? 0u : (cl_uint)((1UL << w) - 1));
+		ns.vmin[i] = (rg.nvalues[i] ? rg.vmin[i] : 0);
+		bits += w;
+	}
+	if (ok)
+	{
+		ns.ncols = (cl_uint)n;
+		ns.reclen = (bits <= 16 ? 2 : 4);
+		char   *d_out = (char *)dev->pool.alloc((size_t)ns.reclen * nslots + 64);
+		const void *a_spec = d_spec;
+		const void *a_recs = recs;
+		const void *a_ns = d_ns;
+		void	   *a_out = d_out;
+		void	   *args[] = { &a_spec, &a_recs, &nslots, &a_ns, &a_out };
+		ok = (d_out &&
+			  hipMemcpyAsync(d_ns, &ns, sizeof(ns), hipMemcpyHostToDevice, stream) == hipSuccess &&
+			  hipModuleLaunchKernel(fn_nw, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
+			  hipStreamSynchronize(stream) == hipSuccess);
+		if (ok)
+			nw.recs = d_out;
+		else if (d_out)
+			dev->pool.release(d_out);
+	}
+	if (!ok)
+		ns.reclen = 0;
+	if (d_spec) dev->pool.release(d_spec);
+	if (d_rg) dev->pool.release(d_rg);
+	if (d_ns) dev->pool.release(d_ns);
+	return nw;
+}
+
+/* may these columns take the narrow form at all: there is one, every one holds integers, and the
+ * form is not switched off */
+bool
+dimrecs_narrow_candidate(int n, const int *narrowable)
+{
+	bool	candidate = (narrowable != nullptr && n >= 1 && !getenv("STROM_HASHJOIN_NO_NARROW_RECS"));
+	for (int i = 0; candidate && i < n; i++)
+		candidate = (narrowable[i] != 0);
+	return candidate;
+}
+
+/* the layout of a standard slot record: a u32 flags word, the values at natural alignment, the
+ * length 8 / 16 / 32 / a multiple of 64.  false: a width that is not 1, 2, 4 or 8. */
+bool
+dimrec_layout(hashjoin_dimrec_spec *spec, int n, const int *cols, const int *attlens)
+{
+	unsigned	off = 4;
+	memset(spec, 0, sizeof(*spec));
+	for (int i = 0; i < n; i++)
+	{
+		if (!(attlens[i] == 1 || attlens[i] == 2 || attlens[i] == 4 || attlens[i] == 8))
+			return false;
+		off = (off + attlens[i] - 1) & ~(unsigned)(attlens[i] - 1);
+		spec->c[i].col = cols[i];
+		spec->c[i].attlen = attlens[i];
+		spec->c[i].offset = off;
+		off += attlens[i];
+	}
+	spec->ncols = n;
+	spec->reclen = (off <= 8 ? 8 : off <= 16 ? 16 : off <= 32 ? 32 : (off + 63) & ~63u);
+	return true;
+}
+
+}	/* namespace */
+
 /*
  * packed slot records of the inner columns cols[] (0-based, attlens[] wide):
  * a u32 flags word (bit 0: row present, bit 1+i: column i NULL) followed by
@@ -872,23 +1016,15 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 
 	if (tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique || n < 0 || n > HASHJOIN_DIMREC_MAXCOLS)
 		return StromError_BadRequestMessage;
-	memset(&spec, 0, sizeof(spec));
-	unsigned	off = 4;
+	if (!dimrec_layout(&spec, n, cols, attlens))
+		return StromError_BadRequestMessage;
+	unsigned	reclen = spec.reclen;
 	std::string	key;
 	for (int i = 0; i < n; i++)
 	{
-		if (!(attlens[i] == 1 || attlens[i] == 2 || attlens[i] == 4 || attlens[i] == 8))
-			return StromError_BadRequestMessage;
-		off = (off + attlens[i] - 1) & ~(unsigned)(attlens[i] - 1);
-		spec.c[i].col = cols[i];
-		spec.c[i].attlen = attlens[i];
-		spec.c[i].offset = offsets[i] = off;
-		off += attlens[i];
+		offsets[i] = spec.c[i].offset;
 		key += std::to_string(cols[i]) + ":" + std::to_string(attlens[i]) + ",";
 	}
-	unsigned	reclen = (off <= 8 ? 8 : off <= 16 ? 16 : off <= 32 ? 32 : (off + 63) & ~63u);
-	spec.ncols = n;
-	spec.reclen = reclen;
 	std::lock_guard<std::mutex> g(tbl->dim_lock);
 	auto	it = tbl->dimrecs.find(key);
 	if (it == tbl->dimrecs.end())
@@ -930,95 +1066,308 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 	if (narrow)
 	{
 		narrow->spec.reclen = 0;
-		bool	candidate = (narrowable != nullptr && n >= 1 && !getenv("STROM_HASHJOIN_NO_NARROW_RECS"));
-		for (int i = 0; candidate && i < n; i++)
-			candidate = (narrowable[i] != 0);
+		bool	candidate = dimrecs_narrow_candidate(n, narrowable);
 		auto	nit = tbl->dimrecs_narrow.find(key);
 		if (candidate && nit == tbl->dimrecs_narrow.end())
-		{
-			/*
-			 * ranges of the wanted columns over the present, non-NULL values -> field widths;
-			 * 1 + n flag bits + the fields must fit 16 or 32 bits
-			 */
-			hashjoin_dimrec_range rg;
-			dimrec_narrow	nw;
-			hashjoin_dimrec_narrow_spec &ns = nw.spec;
-			int			errcode = 0;
-			cl_uint		nslots = tbl->head.rel[0].nslots;
-			hipStream_t	stream = dev->streams[0];
-			(void)hipSetDevice(dev->hip_id);
-			hipFunction_t fn_mm = tbl->prog->get_function(dev, "hashjoin_dimrec_minmax_kernel", &errcode);
-			hipFunction_t fn_nw = tbl->prog->get_function(dev, "hashjoin_dimrec_narrow_kernel", &errcode);
-			char   *d_spec = (char *)dev->pool.alloc(sizeof(spec));
-			char   *d_rg = (char *)dev->pool.alloc(sizeof(rg));
-			char   *d_ns = (char *)dev->pool.alloc(sizeof(ns));
-			unsigned	grid = std::max(1u, std::min<unsigned>((nslots + 255) / 256,
-														   (unsigned)dev->prop.multiProcessorCount * 8));
-			memset(&rg, 0, sizeof(rg));
-			for (int i = 0; i < HASHJOIN_DIMREC_MAXCOLS; i++)
-			{
-				rg.vmin[i] = INT64_MAX;
-				rg.vmax[i] = INT64_MIN;
-			}
-			bool	ok = (fn_mm && fn_nw && d_spec && d_rg && d_ns);
-			if (ok)
-			{
-				const void *a_spec = d_spec;
-				const void *a_recs = it->second.first;
-				void	   *a_rg = d_rg;
-				void	   *args[] = { &a_spec, &a_recs, &nslots, &a_rg };
-				ok = (hipMemcpyAsync(d_spec, &spec, sizeof(spec), hipMemcpyHostToDevice, stream) == hipSuccess &&
-					  hipMemcpyAsync(d_rg, &rg, sizeof(rg), hipMemcpyHostToDevice, stream) == hipSuccess &&
-					  hipModuleLaunchKernel(fn_mm, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
-					  hipMemcpyAsync(&rg, d_rg, sizeof(rg), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-					  hipStreamSynchronize(stream) == hipSuccess);
-			}
-			unsigned	bits = 1 + (unsigned)n;
-			memset(&ns, 0, sizeof(ns));
-			for (int i = 0; ok && i < n; i++)
-			{
-				cl_ulong span = (rg.nvalues[i] ? (cl_ulong)rg.vmax[i] - (cl_ulong)rg.vmin[i] : 0);
-				unsigned w = 0;
-				while (w < 64 && (span >> w) != 0)
-					w++;
-				if (w > 31 || bits + w > 32)
-				{
-					ok = false;
-					break;
-				}
-				ns.shift[i] = bits;
-				ns.mask[i] = (w == 0 ? 0u : (cl_uint)((1UL << w) - 1));
-				ns.vmin[i] = (rg.nvalues[i] ? rg.vmin[i] : 0);
-				bits += w;
-			}
-			if (ok)
-			{
-				ns.ncols = (cl_uint)n;
-				ns.reclen = (bits <= 16 ? 2 : 4);
-				char   *d_out = (char *)dev->pool.alloc((size_t)ns.reclen * nslots + 64);
-				const void *a_spec = d_spec;
-				const void *a_recs = it->second.first;
-				const void *a_ns = d_ns;
-				void	   *a_out = d_out;
-				void	   *args[] = { &a_spec, &a_recs, &nslots, &a_ns, &a_out };
-				ok = (d_out &&
-					  hipMemcpyAsync(d_ns, &ns, sizeof(ns), hipMemcpyHostToDevice, stream) == hipSuccess &&
-					  hipModuleLaunchKernel(fn_nw, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
-					  hipStreamSynchronize(stream) == hipSuccess);
-				if (ok)
-					nw.recs = d_out;
-				else if (d_out)
-					dev->pool.release(d_out);
-			}
-			if (!ok)
-				ns.reclen = 0;
-			if (d_spec) dev->pool.release(d_spec);
-			if (d_rg) dev->pool.release(d_rg);
-			if (d_ns) dev->pool.release(d_ns);
-			nit = tbl->dimrecs_narrow.insert({key, nw}).first;
-		}
+			nit = tbl->dimrecs_narrow.insert({key, dimrecs_narrow_form(tbl, spec, it->second.first,
+																	   tbl->head.rel[0].nslots)}).first;
 		if (candidate && nit != tbl->dimrecs_narrow.end())
 			*narrow = nit->second;
+	}
+	return 0;
+}
+
+namespace {
+
+/* standard records over one relation's slots while a snowflake is flattened: what each column is */
+struct flat_recs {
+	char	   *recs = nullptr;
+	unsigned	reclen = 0;
+	bool		owned = false;			/* a composition of this call: released once it is composed further */
+	struct column {
+		int		served;					/* index into the request's columns, -1: a link column only */
+		int		own_col;				/* the relation's own column (0-based), -1: a descendant's */
+		int		attlen;
+		unsigned offset;
+	};
+	std::vector<column> c;
+};
+
+struct snowflake_request {
+	strom_hashjoin_table *const *tbls;
+	int			ntbls;
+	const int32_t *parent;
+	const int  *link_col;
+	const int  *link_attlen;
+	const snowflake_column *cols;
+	int			ncols;
+};
+
+/* the child's records joined into the parent's, over the parent's slots (hashjoin_compose_dimrec_kernel) */
+int
+compose_child(const snowflake_request &rq, int p, flat_recs *pr, int c, const flat_recs &cr, bool keep_link)
+{
+	strom_hashjoin_table *ptbl = rq.tbls[p - 1], *ctbl = rq.tbls[c - 1];
+	Device	   *dev = ptbl->dev;
+	hashjoin_compose_spec cs;
+	hashjoin_dimrec_spec lay;
+	std::vector<flat_recs::column> out;
+	int			cols[HASHJOIN_DIMREC_MAXCOLS], lens[HASHJOIN_DIMREC_MAXCOLS];
+	int			link = -1;
+
+	memset(&cs, 0, sizeof(cs));
+	for (size_t i = 0; i < pr->c.size(); i++)
+		if (pr->c[i].own_col == rq.link_col[c - 1] && pr->c[i].attlen == rq.link_attlen[c - 1])
+			link = (int)i;
+	if (link < 0)
+		return StromError_BadRequestMessage;
+	for (int from_child = 0; from_child < 2; from_child++)
+	{
+		const flat_recs &src = (from_child ? cr : *pr);
+		for (size_t i = 0; i < src.c.size(); i++)
+		{
+			if (!from_child && (int)i == link && src.c[i].served < 0 && !keep_link)
+				continue;			/* the link column is kept only if the query serves it, or a later child needs it */
+			if (out.size() == HASHJOIN_DIMREC_MAXCOLS)
+				return StromError_BadRequestMessage;
+			auto   &cc = cs.c[out.size()];
+			cc.from_child = from_child;
+			cc.attlen = src.c[i].attlen;
+			cc.src_offset = src.c[i].offset;
+			cc.src_nullbit = 1 + (cl_uint)i;
+			cols[out.size()] = -1;
+			lens[out.size()] = src.c[i].attlen;
+			out.push_back(src.c[i]);
+			if (from_child)
+				out.back().own_col = -1;
+		}
+	}
+	if (!dimrec_layout(&lay, (int)out.size(), cols, lens))
+		return StromError_BadRequestMessage;
+	for (size_t i = 0; i < out.size(); i++)
+		cs.c[i].offset = out[i].offset = lay.c[i].offset;
+	cs.ncols = lay.ncols;
+	cs.reclen = lay.reclen;
+	cs.parent_reclen = pr->reclen;
+	cs.child_reclen = cr.reclen;
+	cs.link_attlen = pr->c[link].attlen;
+	cs.link_offset = pr->c[link].offset;
+	cs.link_nullbit = 1 + (cl_uint)link;
+
+	int			errcode = 0;
+	cl_uint		nslots = ptbl->head.rel[0].nslots;
+	cl_long		child_key_min = ctbl->head.rel[0].key_min;
+	cl_uint		child_nslots = ctbl->head.rel[0].nslots;
+	hipStream_t	stream = dev->streams[0];
+	(void)hipSetDevice(dev->hip_id);
+	hipFunction_t fn = ptbl->prog->get_function(dev, "hashjoin_compose_dimrec_kernel", &errcode);
+	if (!fn)
+		return errcode;
+	char	   *d_recs = (char *)dev->pool.alloc((size_t)cs.reclen * nslots + 64);
+	char	   *d_spec = (char *)dev->pool.alloc(sizeof(cs));
+	int			rc = StromError_OutOfMemory;
+	if (d_recs && d_spec)
+	{
+		const void *a_spec = d_spec;
+		const void *a_precs = pr->recs;
+		const void *a_crecs = cr.recs;
+		void	   *a_recs = d_recs;
+		void	   *args[] = { &a_spec, &a_precs, &nslots, &a_crecs, &child_key_min, &child_nslots, &a_recs };
+		unsigned	grid = std::max(1u, std::min<unsigned>((nslots + 255) / 256,
+													   (unsigned)dev->prop.multiProcessorCount * 8));
+		/* (read on every call: tests walk the grid stride of a small table with it) */
+		const char *cap = getenv("STROM_HASHJOIN_DIMREC_MAX_GRID");
+		if (cap && atoi(cap) >= 1)
+			grid = std::min<unsigned>(grid, (unsigned)atoi(cap));
+		rc = ((hipMemcpyAsync(d_spec, &cs, sizeof(cs), hipMemcpyHostToDevice, stream) == hipSuccess &&
+			   hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
+			   hipStreamSynchronize(stream) == hipSuccess) ? 0 : StromError_HipInternal);
+	}
+	if (d_spec) dev->pool.release(d_spec);
+	if (rc != 0)
+	{
+		if (d_recs) dev->pool.release(d_recs);
+		return rc;
+	}
+	if (pr->owned)
+		dev->pool.release(pr->recs);
+	pr->recs = d_recs;
+	pr->reclen = cs.reclen;
+	pr->owned = true;
+	pr->c = out;
+	return 0;
+}
+
+/* relation d's standard records for its served columns and its children's link columns, every child
+ * (itself flattened) composed into them */
+int
+flatten_relation(const snowflake_request &rq, int d, flat_recs *fr)
+{
+	int			cols[HASHJOIN_DIMREC_MAXCOLS], lens[HASHJOIN_DIMREC_MAXCOLS];
+	unsigned	offs[HASHJOIN_DIMREC_MAXCOLS];
+	void	   *recs = nullptr;
+
+	for (int k = 0; k < rq.ncols; k++)
+		if (rq.cols[k].rel == d)
+			fr->c.push_back({k, rq.cols[k].col, rq.cols[k].attlen, 0});
+	for (int c = d + 1; c <= rq.ntbls; c++)
+	{
+		if (rq.parent[c - 1] != d)
+			continue;
+		bool	have = false;
+		for (auto &e : fr->c)
+			have = have || (e.own_col == rq.link_col[c - 1] && e.attlen == rq.link_attlen[c - 1]);
+		if (!have)
+			fr->c.push_back({-1, rq.link_col[c - 1], rq.link_attlen[c - 1], 0});
+	}
+	if (fr->c.size() > HASHJOIN_DIMREC_MAXCOLS)
+		return StromError_BadRequestMessage;
+	for (size_t i = 0; i < fr->c.size(); i++)
+	{
+		cols[i] = fr->c[i].own_col;
+		lens[i] = fr->c[i].attlen;
+	}
+	int			rc = hashjoin_table_dimrecs(rq.tbls[d - 1], (int)fr->c.size(), cols, lens, offs, &recs, &fr->reclen);
+	if (rc != 0)
+		return rc;
+	fr->recs = (char *)recs;
+	for (size_t i = 0; i < fr->c.size(); i++)
+		fr->c[i].offset = offs[i];
+	for (int c = d + 1; rc == 0 && c <= rq.ntbls; c++)
+	{
+		if (rq.parent[c - 1] != d)
+			continue;
+		flat_recs	child;
+		bool		keep_link = false;
+		for (int c2 = c + 1; c2 <= rq.ntbls; c2++)
+			keep_link = keep_link || (rq.parent[c2 - 1] == d && rq.link_col[c2 - 1] == rq.link_col[c - 1] &&
+									  rq.link_attlen[c2 - 1] == rq.link_attlen[c - 1]);
+		rc = flatten_relation(rq, c, &child);
+		if (rc == 0)
+			rc = compose_child(rq, d, fr, c, child, keep_link);
+		if (child.owned)
+			rq.tbls[c - 1]->dev->pool.release(child.recs);
+	}
+	if (rc != 0 && fr->owned)
+	{
+		rq.tbls[d - 1]->dev->pool.release(fr->recs);
+		fr->owned = false;
+	}
+	return rc;
+}
+
+}	/* namespace */
+
+int
+strom::hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, const int32_t *parent,
+								  const int *link_col, const int *link_attlen, int root,
+								  snowflake_column *cols, int ncols,
+								  void **p_recs, unsigned *p_reclen, dimrec_narrow *narrow)
+{
+	strom_hashjoin_table *rtbl = tbls[root - 1];
+	snowflake_request rq = { tbls, ntbls, parent, link_col, link_attlen, cols, ncols };
+	int			narrowable[HASHJOIN_DIMREC_MAXCOLS] = {};
+	bool		leaf = true;
+
+	if (ncols > HASHJOIN_DIMREC_MAXCOLS)
+		return StromError_BadRequestMessage;
+	for (int d = root + 1; d <= ntbls; d++)
+		leaf = leaf && (parent[d - 1] != root);
+	for (int k = 0; k < ncols; k++)
+		narrowable[k] = cols[k].narrowable;
+	narrow->spec.reclen = 0;
+	if (leaf)
+	{
+		/* nothing hangs below it: the one-table records, as the star takes them */
+		int			own[HASHJOIN_DIMREC_MAXCOLS] = {}, lens[HASHJOIN_DIMREC_MAXCOLS] = {};
+		unsigned	offs[HASHJOIN_DIMREC_MAXCOLS] = {};
+		for (int k = 0; k < ncols; k++)
+		{
+			own[k] = cols[k].col;
+			lens[k] = cols[k].attlen;
+		}
+		int		rc = hashjoin_table_dimrecs(rtbl, ncols, own, lens, offs, p_recs, p_reclen, narrowable, narrow);
+		for (int k = 0; rc == 0 && k < ncols; k++)
+		{
+			cols[k].recpos = k;
+			cols[k].offset = offs[k];
+		}
+		return rc;
+	}
+	/* the subtree as text: the served columns in the request's order, then every relation of the tree
+	 * by serial number with its parent and link (one that is not below 'root' serves no column here
+	 * and changes nothing but the key) */
+	std::string	key;
+	for (int k = 0; k < ncols; k++)
+		key += std::to_string(cols[k].rel) + "." + std::to_string(cols[k].col) + ":" + std::to_string(cols[k].attlen) + ",";
+	std::vector<char> below(ntbls + 1, 0);
+	below[root] = 1;
+	for (int d = root + 1; d <= ntbls; d++)
+	{
+		if (parent[d - 1] == 0 || !below[parent[d - 1]])
+			continue;
+		below[d] = 1;
+		key += "|" + std::to_string(d) + "^" + std::to_string(parent[d - 1]) + "#" + std::to_string(tbls[d - 1]->serial) +
+			"@" + std::to_string(link_col[d - 1]) + ":" + std::to_string(link_attlen[d - 1]);
+	}
+	for (int k = 0; k < ncols; k++)
+		if (cols[k].rel < 1 || cols[k].rel > ntbls || !below[cols[k].rel])
+			return StromError_BadRequestMessage;
+	/* never two tables' dim_lock at once: look, flatten without the root's lock (each relation's
+	 * records are fetched under its own), then take the root's again to keep the result */
+	bool		hit;
+	{
+		std::lock_guard<std::mutex> g(rtbl->dim_lock);
+		hit = (rtbl->composed.find(key) != rtbl->composed.end());
+	}
+	flat_recs	fr;
+	if (!hit)
+	{
+		int		rc = flatten_relation(rq, root, &fr);
+		if (rc != 0)
+			return rc;
+	}
+	std::lock_guard<std::mutex> g(rtbl->dim_lock);
+	auto	it = rtbl->composed.find(key);
+	if (it == rtbl->composed.end())
+	{
+		if (!fr.owned)
+			return StromError_BadRequestMessage;		/* (released between the two looks: not by a caller that holds it) */
+		strom_hashjoin_table::composed_dimrecs cd;
+		int			none[HASHJOIN_DIMREC_MAXCOLS], lens[HASHJOIN_DIMREC_MAXCOLS];
+		cd.recs = fr.recs;
+		cd.recpos.assign(ncols, -1);
+		for (size_t i = 0; i < fr.c.size(); i++)
+		{
+			none[i] = -1;
+			lens[i] = fr.c[i].attlen;
+			if (fr.c[i].served >= 0)
+				cd.recpos[fr.c[i].served] = (int)i;
+		}
+		dimrec_layout(&cd.spec, (int)fr.c.size(), none, lens);
+		it = rtbl->composed.insert({key, cd}).first;
+	}
+	else if (fr.owned)
+		rtbl->dev->pool.release(fr.recs);				/* another caller was first */
+	auto   &cd = it->second;
+	*p_recs = cd.recs;
+	*p_reclen = cd.spec.reclen;
+	/* (every link column that is not served is gone by now: the record's columns are the served ones) */
+	int			recints[HASHJOIN_DIMREC_MAXCOLS];
+	for (int k = 0; k < ncols; k++)
+	{
+		cols[k].recpos = cd.recpos[k];
+		cols[k].offset = cd.spec.c[cd.recpos[k]].offset;
+		recints[cd.recpos[k]] = narrowable[k];
+	}
+	if (dimrecs_narrow_candidate((int)cd.spec.ncols, recints))
+	{
+		if (!cd.narrow_tried)
+		{
+			cd.narrow = dimrecs_narrow_form(rtbl, cd.spec, cd.recs, rtbl->head.rel[0].nslots);
+			cd.narrow_tried = true;
+		}
+		*narrow = cd.narrow;
 	}
 	return 0;
 }

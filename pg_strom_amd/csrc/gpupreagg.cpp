@@ -2623,6 +2623,138 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 	return 0;
 }
 
+/*
+ * The mapping of strom_submit_gpupreagg_lookup_snowflake: the tree flattened into its roots' slot records
+ * (hashjoin_snowflake_dimrecs), and *m the star of those roots -- a virtual column of any relation of a
+ * subtree points at its field in the ROOT's record.  The checks, their order and their codes are the
+ * star's (build_fold_mapping); what is new is said where it is checked.
+ */
+int
+build_snowflake_mapping(strom_gpupreagg *sess, strom_hashjoin_table *const *tbls, int ntbls,
+						const int32_t *parent, const int32_t *link_type_oids, strom_dstore *outer,
+						int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
+						fold_mapping *m)
+{
+	int32_t		root_of[STROM_LOOKUP_SNOWFLAKE_MAXRELS], col_root[GPUPREAGG_JOINED_MAXCOLS];
+	int			link_col[STROM_LOOKUP_SNOWFLAKE_MAXRELS] = {}, link_attlen[STROM_LOOKUP_SNOWFLAKE_MAXRELS] = {};
+
+	if (!sess || sess->hashed || !sess->has_domain || !tbls || !parent || !link_type_oids || !outer ||
+		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids)
+		return StromError_BadRequestMessage;
+	int			nroots = strom_gpupreagg_lookup_snowflake_roots(ntbls, parent, ncols, src_depth, root_of, col_root);
+	if (nroots < 1)
+		return StromError_BadRequestMessage;
+	for (int d = 1; d <= ntbls; d++)
+		if (!tbls[d - 1])
+			return StromError_BadRequestMessage;
+	int			outer_ncols = (int)outer->head.ncols;
+	if (outer->head.format != KDS_FORMAT_COLUMN || outer->dindex != sess->dev->dindex)
+		return StromError_BadRequestMessage;
+	m->ncols = ncols;
+	m->nrels = nroots;
+	for (int d = 1; d <= ntbls; d++)
+	{
+		int			key_attno = 0, tbl_dindex = -1, has_outer_qual = 0;
+		cl_long		key_min;
+		cl_uint		nslots;
+		if (hashjoin_table_direct_info(tbls[d - 1], &key_min, &nslots, &key_attno, &tbl_dindex, &has_outer_qual) != 0 ||
+			has_outer_qual || key_attno < 1 || tbl_dindex != sess->dev->dindex)
+			return StromError_BadRequestMessage;
+		if (parent[d - 1] == 0)
+		{
+			int		r = root_of[d - 1] - 1;
+			if (key_attno > outer_ncols)
+				return StromError_BadRequestMessage;
+			m->key_col[r] = key_attno - 1;
+			m->key_min[r] = key_min;
+			m->nslots[r] = nslots;
+			continue;
+		}
+		/* the table's program names a column of its PARENT relation; its type is the caller's word (the
+		 * build kernel holds it against the parent's rows: DataStoreCorruption) */
+		int		oid = link_type_oids[d - 1];
+		if (!(oid == STROM_INT4OID || oid == STROM_DATEOID || oid == STROM_INT8OID))
+			return StromError_BadRequestMessage;
+		link_col[d - 1] = key_attno - 1;
+		link_attlen[d - 1] = type_length(oid);
+	}
+	for (int i = 0; i < ncols; i++)
+		if (src_colidx[i] < 0)
+			return StromError_BadRequestMessage;
+	(void)hipSetDevice(sess->dev->hip_id);
+	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
+	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_BadRequestMessage;
+	const kern_data_store *oh = (const kern_data_store *)ohead.data();
+	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
+		return StromError_BadRequestMessage;
+	for (int r = 0; r < nroots; r++)
+	{
+		int		len = m->key_attlen[r] = oh->colmeta[m->key_col[r]].attlen;
+		if (!(len == 4 || len == 8))
+			return StromError_BadRequestMessage;
+	}
+	for (int i = 0; i < ncols; i++)
+	{
+		memset(&m->c[i], 0, sizeof(m->c[i]));
+		m->c[i].depth = col_root[i];
+		m->c[i].col = src_colidx[i];
+		if (src_depth[i] == 0)
+		{
+			int		oid = type_oids[i];
+			int		attlen = ((oid == STROM_TEXTOID || oid == STROM_BPCHARNOID) ? -1 : type_length(oid));
+			if (src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen)
+				return StromError_DataStoreCorruption;
+		}
+	}
+	for (int d = 1; d <= ntbls; d++)
+	{
+		if (parent[d - 1] != 0)
+			continue;
+		/* the served columns of this root's whole subtree, in one composed record per slot of the root */
+		int			r = root_of[d - 1] - 1;
+		snowflake_column cols[HASHJOIN_DIMREC_MAXCOLS];
+		int			which[HASHJOIN_DIMREC_MAXCOLS], n = 0;
+		unsigned	reclen = 0;
+		void	   *recs = nullptr;
+		dimrec_narrow nw;
+		m->inner_mask[r] = 0;
+		for (int i = 0; i < ncols; i++)
+		{
+			if (col_root[i] != r + 1)
+				continue;
+			if (n == HASHJOIN_DIMREC_MAXCOLS)
+				return StromError_BadRequestMessage;
+			int		oid = (type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
+			cols[n] = { src_depth[i], src_colidx[i], type_length(oid),
+						!(type_is_float(oid) || oid == STROM_NUMERICOID), 0, 0 };
+			which[n++] = i;
+			m->inner_mask[r] |= ((uint64_t)1 << i);
+		}
+		int			rc = hashjoin_snowflake_dimrecs(tbls, ntbls, parent, link_col, link_attlen, d, cols, n,
+													&recs, &reclen, &nw);
+		if (rc != 0)
+			return rc;
+		bool		narrow = (nw.spec.reclen != 0);
+		m->recs[r] = (cl_ulong)(uintptr_t)(narrow ? nw.recs : recs);
+		m->reclen[r] = (narrow ? nw.spec.reclen : reclen);
+		m->narrow[r] = (narrow ? 1 : 0);
+		for (int k = 0; k < n; k++)
+		{
+			auto   &c = m->c[which[k]];
+			c.recoff = (narrow ? 0 : cols[k].offset);
+			c.nullbit = 1 + cols[k].recpos;
+			if (narrow)
+			{
+				c.nshift = nw.spec.shift[cols[k].recpos];
+				c.nmask = nw.spec.mask[cols[k].recpos];
+				c.nmin = nw.spec.vmin[cols[k].recpos];
+			}
+		}
+	}
+	return 0;
+}
+
 /* the mapping as gpupreagg_dense_joined / _lookup read it (one relation) */
 std::shared_ptr<std::vector<char>>
 write_joined_map(const fold_mapping &m)
@@ -2678,24 +2810,14 @@ write_star_map(const fold_mapping &m)
  * The three fused folds (strom_hip.h): the rows a finished GpuHashJoin produced, straight from its result
  * pairs (gpupreagg_dense_joined); the join as a lookup inside the aggregate's own pass over the outer chunk,
  * no join request at all (gpupreagg_dense_lookup); a star of such lookups, one table per relation
- * (gpupreagg_dense_lookup_star)
+ * (gpupreagg_dense_lookup_star) -- and a snowflake, which is the lookup or the star it flattens to.  One launch
+ * path: the request of a mapping, whichever builder described it.
  */
 static strom_task *
-submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *join_handle,
-					   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
-					   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
-					   strom_done_cb done, void *arg, int *p_errcode)
+launch_fused_fold(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jtask, const fold_mapping &m,
+				  strom_dstore *outer, strom_done_cb done, void *arg, int *p_errcode)
 {
-	STROM_ABI_TRY
-	int		dummy;
-	if (!p_errcode)
-		p_errcode = &dummy;
-	strom_task_impl *jtask = static_cast<strom_task_impl *>(join_handle);
-	fold_mapping m;
 	preagg_request req;
-	*p_errcode = build_fold_mapping(sess, entry, jtask, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids, &m);
-	if (*p_errcode != 0)
-		return nullptr;
 	req.sess = sess;
 	req.kds_dev = outer;
 	req.format = KDS_FORMAT_COLUMN;
@@ -2705,7 +2827,7 @@ submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *joi
 	{
 		/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
 		 * all relations: no define block -- the kernel keeps a row's records in registers) */
-		req.star_defs = star_mapping_defines(ntbls, m.key_attlen, m.reclen, m.narrow, m.inner_mask);
+		req.star_defs = star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask);
 		if (req.star_defs.empty())
 		{
 			*p_errcode = StromError_BadRequestMessage;
@@ -2739,6 +2861,25 @@ submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *joi
 	strom_task_impl *task = task_create(sess->dev, done, arg);
 	program_run_or_park(req.prog ? req.prog : sess->prog, [task, req]() { gpupreagg_launch(task, req); });
 	return task;
+}
+
+/* _joined, _lookup and _lookup_star: build_fold_mapping, then the launch */
+static strom_task *
+submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *join_handle,
+					   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
+					   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
+					   strom_done_cb done, void *arg, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	strom_task_impl *jtask = static_cast<strom_task_impl *>(join_handle);
+	fold_mapping m;
+	*p_errcode = build_fold_mapping(sess, entry, jtask, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids, &m);
+	if (*p_errcode != 0)
+		return nullptr;
+	return launch_fused_fold(sess, entry, jtask, m, outer, done, arg, p_errcode);
 	STROM_ABI_CATCH(nullptr, p_errcode)
 }
 
@@ -2787,6 +2928,71 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 	/* (one relation is the one-table call, its kernel and its error codes) */
 	return submit_gpupreagg_fused(sess, (ntbls == 1 && tbls) ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
 								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode);
+}
+
+extern "C" int
+strom_gpupreagg_lookup_snowflake_roots(int ntbls, const int32_t *parent, int ncols, const int32_t *src_depth,
+									   int32_t *root_of, int32_t *col_root)
+{
+	/* relation d hangs on a fact column (parent 0: a root, numbered 1 .. in the order they come) or on a
+	 * column of an EARLIER relation, whose root is then its own */
+	int32_t		roots[STROM_LOOKUP_SNOWFLAKE_MAXRELS];
+	int			nroots = 0;
+	if (ntbls < 1 || ntbls > STROM_LOOKUP_SNOWFLAKE_MAXRELS || !parent || ncols < 0 || (ncols > 0 && !src_depth))
+		return -1;
+	for (int d = 1; d <= ntbls; d++)
+	{
+		if (parent[d - 1] < 0 || parent[d - 1] >= d)
+			return -1;
+		roots[d - 1] = (parent[d - 1] == 0 ? ++nroots : roots[parent[d - 1] - 1]);
+	}
+	if (nroots > STROM_LOOKUP_STAR_MAXRELS)
+		return -1;
+	for (int i = 0; i < ncols; i++)
+	{
+		if (src_depth[i] < 0 || src_depth[i] > ntbls)
+			return -1;
+		if (col_root)
+			col_root[i] = (src_depth[i] == 0 ? 0 : roots[src_depth[i] - 1]);
+	}
+	if (root_of)
+		memcpy(root_of, roots, sizeof(int32_t) * ntbls);
+	return nroots;
+}
+
+extern "C" strom_task *
+strom_submit_gpupreagg_lookup_snowflake(strom_gpupreagg *sess,
+										strom_hashjoin_table *const *tbls, int ntbls,
+										const int32_t *parent, const int32_t *link_type_oids,
+										strom_dstore *outer,
+										int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+										const int32_t *type_oids,
+										strom_done_cb done, void *arg, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	if (!parent || ntbls < 1 || ntbls > STROM_LOOKUP_SNOWFLAKE_MAXRELS)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	/* (no relation hangs on another: the star call, one relation: the one-table call -- their code
+	 * paths and their error codes) */
+	bool	star = true;
+	for (int d = 1; d <= ntbls; d++)
+		star = star && (parent[d - 1] == 0);
+	if (star)
+		return strom_submit_gpupreagg_lookup_star(sess, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids,
+												  done, arg, p_errcode);
+	fold_mapping m;
+	*p_errcode = build_snowflake_mapping(sess, tbls, ntbls, parent, link_type_oids, outer, ncols, src_depth, src_colidx,
+										 type_oids, &m);
+	if (*p_errcode != 0)
+		return nullptr;
+	return launch_fused_fold(sess, m.nrels == 1 ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, m, outer, done, arg, p_errcode);
+	STROM_ABI_CATCH(nullptr, p_errcode)
 }
 
 /*

@@ -262,6 +262,26 @@ struct dimrec_narrow {
 int			hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols, const int *attlens,
 								   unsigned *offsets, void **p_recs, unsigned *p_reclen,
 								   const int *narrowable = nullptr, dimrec_narrow *narrow = nullptr);
+/*
+ * A SNOWFLAKE below relation 'root' flattened into root's slot records: tbls[d - 1] is relation d as
+ * hashjoin_table_dimrecs takes it, parent[d - 1] the relation whose column link_col[d - 1] (0-based,
+ * link_attlen[d - 1] bytes wide) is d's key, 0 for a relation keyed by a fact column.  cols[] are the
+ * served columns of root's subtree; each gets its place in the composed STANDARD record (recpos: its
+ * column there, NULL bit 1 + recpos; offset), the narrow form is in *narrow as for
+ * hashjoin_table_dimrecs.  Composed records are built on first use and kept with the root table.
+ */
+struct snowflake_column {
+	int			rel;			/* 1-based */
+	int			col;			/* 0-based */
+	int			attlen;
+	int			narrowable;
+	int			recpos;			/* out */
+	unsigned	offset;			/* out */
+};
+int			hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, const int32_t *parent,
+									   const int *link_col, const int *link_attlen, int root,
+									   snowflake_column *cols, int ncols,
+									   void **p_recs, unsigned *p_reclen, dimrec_narrow *narrow);
 int			hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 									   int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual = nullptr);
 /* gpupreagg.cpp, for the RCCL merge (parallel.cpp) */

@@ -89,6 +89,23 @@ def lookup_star_defines(relations):
     return buf.value.decode()
 
 
+def lookup_snowflake_roots(parents, column_depths):
+    """which star a snowflake flattens to (strom_gpupreagg_lookup_snowflake_roots; no device needed):
+    parents[d - 1] is 0 for a relation joined on a fact column, p < d for one joined on a column of
+    relation p; column_depths the depth 0 .. len(parents) of every virtual column.  Returns
+    (number of roots, [root ordinal 1.. of each relation], [0 or the root ordinal of each column]);
+    ValueError for an invalid tree."""
+    par = np.array(list(parents), dtype=np.int32)
+    dep = np.array(list(column_depths), dtype=np.int32)
+    root_of = np.zeros(max(1, len(par)), dtype=np.int32)
+    col_root = np.zeros(max(1, len(dep)), dtype=np.int32)
+    rc = lib.strom_gpupreagg_lookup_snowflake_roots(len(par), par.ctypes.data, len(dep), dep.ctypes.data,
+                                                    root_of.ctypes.data, col_root.ctypes.data)
+    if rc < 0:
+        raise ValueError("no snowflake: parents %r, column depths %r" % (list(parents), list(column_depths)))
+    return rc, root_of[:len(par)].tolist(), col_root[:len(dep)].tolist()
+
+
 def _column_mapping(columns):
     """columns [(depth, attno, sqltype)] as join_to_column takes them -> the (src_depth, src_colidx,
     type_oids) int32 arrays of the strom_submit_gpupreagg_joined / _lookup / _lookup_star calls"""
@@ -281,6 +298,36 @@ class GpuPreAgg(object):
         if not task:
             raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_star")
         return (task, chunk, (depth, colidx, oids, tbls))
+
+    def submit_lookup_snowflake(self, joins, parents, chunk, columns, link_types=None):
+        """fact JOIN d1 JOIN d2 ... GROUP BY where a relation may be keyed by ANOTHER relation's column
+        (strom_submit_gpupreagg_lookup_snowflake): parents[d - 1] is 0 for a relation joined on a fact
+        column, p < d for one joined on a column of relation p -- joins[d - 1]'s program names that
+        column as its outer key, link_types[d - 1] is its sqltype ("int4", "date", "int8"; ignored
+        where the parent is 0, None allowed where every parent is 0).  The dimensions are joined to
+        each other once, into the root tables' slot records; the fold is the one-table lookup (one
+        root) or the star (2 .. 4 roots).  columns as in submit_lookup_star, depth 0 .. len(joins)."""
+        from .kds import column_type_oid
+        depth, colidx, oids = _column_mapping(columns)
+        tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
+        par = np.array(list(parents), dtype=np.int32)
+        if len(par) != len(joins):
+            raise ValueError("one parent per relation")
+        if link_types is None:
+            link_types = [None] * len(joins)
+        links = np.array([column_type_oid(t) if (t is not None and p != 0) else 0
+                          for t, p in zip(link_types, par)], dtype=np.int32)
+        if len(links) != len(joins):
+            raise ValueError("one link type per relation")
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpupreagg_lookup_snowflake(self.session, tbls, len(joins),
+                                                           par.ctypes.data if len(par) else None,
+                                                           links.ctypes.data if len(links) else None, chunk.handle,
+                                                           len(columns), depth.ctypes.data, colidx.ctypes.data,
+                                                           oids.ctypes.data, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_snowflake")
+        return (task, chunk, (depth, colidx, oids, tbls, par, links))
 
     def collect(self, pending):
         """returns (status, perfmon): status 0 folded, 2 CpuReCheck (not folded)"""

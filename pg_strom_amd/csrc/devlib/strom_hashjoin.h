@@ -702,7 +702,21 @@ gpuhashjoin_main(kern_hashjoin *__restrict__ khashjoin,
 #ifndef HASHJOIN_LDS_QUADS
 #define HASHJOIN_LDS_QUADS		8
 #endif
-#define HASHJOIN_MAX_QUADS		(HASHJOIN_LDS_QUADS > HASHJOIN_QUADS ? HASHJOIN_LDS_QUADS : HASHJOIN_QUADS)
+/* the most quads any of the one-pass kernels below is instantiated with: it sizes the stage's
+ * per-quad wave totals, which every one of them indexes with its own QUADS */
+#define HASHJOIN_MAX2(a,b)		((a) > (b) ? (a) : (b))
+#define HASHJOIN_MAX_QUADS		HASHJOIN_MAX2(HASHJOIN_MAX2(HASHJOIN_LDS_QUADS, HASHJOIN_FAST_QUADS), HASHJOIN_QUADS)
+/*
+ * A geometry the header cannot serve fails the program build; it never runs.  A thread keeps
+ * 4 x QUADS rows of every outer column, their match words and (with a pulled-up qual) their
+ * error words in registers.  The kernels that probe through the caches have been swept and are
+ * tested up to 8 quads (profiles/r03_c3_sweep.txt), the LDS variant, alone on its CU, up to 16
+ * (scripts/gpu_hashjoin_lds_probe.py): nothing beyond that is known to be right, so it is refused.
+ */
+static_assert(HASHJOIN_QUADS >= 1 && HASHJOIN_QUADS <= 8 &&
+			  HASHJOIN_FAST_QUADS >= 1 && HASHJOIN_FAST_QUADS <= 8 &&
+			  HASHJOIN_LDS_QUADS >= 1 && HASHJOIN_LDS_QUADS <= 16,
+			  "HASHJOIN_QUADS and HASHJOIN_FAST_QUADS are 1..8, HASHJOIN_LDS_QUADS is 1..16");
 /* matches are appended to the stage in groups of quads that fit it */
 #define HASHJOIN_STAGE_ENTRIES	HASHJOIN_STAGE
 #define HASHJOIN_APPEND_QUADS(Q)	((Q) * HASHJOIN_BLOCK * 4 <= HASHJOIN_STAGE ? (Q)		\
@@ -775,6 +789,8 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 						   const hashjoin_index *hjidx,
 						   const kern_data_store *kds)
 {
+	static_assert(QUADS >= 1 && QUADS <= HASHJOIN_MAX_QUADS,
+				  "stage.wave_total[] has a row per quad of the widest kernel");
 	__shared__ hashjoin_stage stage;
 	extern __shared__ __attribute__((aligned(16))) cl_uint lds_slots[];
 	const cl_uint TILE_ROWS = HASHJOIN_BLOCK * 4 * QUADS;

@@ -489,12 +489,21 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		int		generic_rows = 64;								/* HASHJOIN_GENERIC_ROWS */
 		if (const char *v = getenv("STROM_HASHJOIN_GENERIC_ROWS"))
 			generic_rows = std::max(1, atoi(v));
+		/* the tile of each one-pass kernel, from the knobs its program was built with (runtime.cpp:
+		 * tunable_options; strom_hashjoin.h refuses what it cannot serve): block x 4 x quads rows */
 		int		lds_quads = 8;									/* HASHJOIN_LDS_QUADS */
 		if (const char *v = getenv("STROM_HASHJOIN_LDS_QUADS"))
 			lds_quads = std::max(1, atoi(v));
+		int		fast_quads = 4;									/* HASHJOIN_FAST_QUADS */
+		if (const char *v = getenv("STROM_HASHJOIN_FAST_QUADS"))
+			fast_quads = std::max(1, atoi(v));
+		int		keyed_quads = 2;								/* HASHJOIN_QUADS */
+		if (const char *v = getenv("STROM_HASHJOIN_QUADS"))
+			keyed_quads = std::max(1, atoi(v));
 		/* (the general kernel sizes its tiles from the grid: one row per thread is the smallest) */
 		size_t	tile_rows = lds_slot_bytes ? (size_t)block * 4 * lds_quads
-			: fast ? (size_t)block * 4 * 2 : (size_t)block;
+			: fast_keyed ? (size_t)block * 4 * keyed_quads
+			: fast ? (size_t)block * 4 * fast_quads : (size_t)block;
 		size_t	ntiles = (req.nrows + tile_rows - 1) / tile_rows;
 		(void)generic_rows;
 		int		per_cu = 0;
@@ -504,6 +513,10 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		if (const char *v = getenv("STROM_HASHJOIN_BLOCKS_PER_CU"))
 			per_cu = std::max(1, atoi(v));
 		size_t	grid = std::max<size_t>(1, std::min<size_t>(ntiles, (size_t)dev->prop.multiProcessorCount * per_cu));
+		/* a cap on the work-groups of the main kernel, one-pass and general alike (tests: one
+		 * work-group walks many tiles of a small chunk); read per launch, no part of the program */
+		if (const char *v = getenv("STROM_HASHJOIN_MAX_GRID"))
+			grid = std::min<size_t>(grid, (size_t)std::max(1, atoi(v)));
 		void	   *a_khj = d_khj;
 		const void *a_km = tbl->d_kmhash;
 		const void *a_ix = tbl->d_index;

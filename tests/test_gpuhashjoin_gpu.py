@@ -192,9 +192,12 @@ def test_c3_shape_properties_at_1e8():
 @pytest.mark.parametrize("nfact", [1, 255, 4096, 16383, 16384, 16385, 40001])
 @pytest.mark.parametrize("fanout", [1, 40])
 def test_general_kernel_tile_and_slice_boundaries(nfact, fanout):
-    """the general kernel counts per 16k-row tile and emits per 4096-row slice
-    through a 32 KB LDS stage; a slice whose matches do not fit the stage
-    (fan-out 40) takes the direct path.  A row map forces the general kernel."""
+    """the general kernel (a row map forces it) at one row per thread: the host launches
+    min(ceil(rows / 256), what the chip holds) work-groups and the kernel gives a thread
+    ceil(rows / (work-groups x 256)) rows, which is 1 at every size here -- 256-row tiles, slice 0
+    alone, several work-groups, a ragged last tile, the 32 KB LDS stage (fan-out 1) and the direct
+    path of a slice whose matches do not fit it (fan-out 40: 256 x 40 records).  Larger tiles, the
+    other slices and a work-group that walks several tiles: test_hashjoin_edges_gpu.py."""
     rng = np.random.default_rng(1000 + nfact + fanout)
     ndim_keys = 300
     pk = np.repeat(np.arange(ndim_keys, dtype=np.int32), fanout)

@@ -398,6 +398,22 @@ strom_task *strom_submit_gpupreagg_chunk(strom_devprog_key key,
  *   with an exactly-sized buffer, 4330-4425).  A row-level CpuReCheck is
  *   reported as the chunk errcode: the reference has no CPU path for join
  *   rows ("CPU Recheck not implemented yet", 2948-2952).
+ *
+ *   Join types.  A (rel ..) of the join program may carry (jointype inner | left | semi | anti),
+ *   default inner.  The slot of such a relation in a result record:
+ *     inner  the offset of the matched entry, one record per candidate;
+ *     left   the same, or 0 for a prefix without a candidate (one record, every column of the
+ *            relation NULL);
+ *     semi   0, ONE record for a prefix with at least one candidate;
+ *     anti   0, one record for a prefix with none (NOT EXISTS: a NULL key has no candidate).
+ *   A candidate is an entry whose keys are equal (a NULL never is) and for which the rel's qual
+ *   -- the ON clause -- is true.  OFFSET 0 IS NEVER AN ENTRY: the table head sits there, so 0 in a
+ *   record means "no entry" and every projection below makes the relation's columns NULL without
+ *   reading the table.  RIGHT and FULL joins are out of scope: they need "entry was matched"
+ *   flags that outlive a chunk; the code generator refuses them by name.  A one-relation LEFT /
+ *   SEMI / ANTI join on one integer-like key without a qual takes the one-pass kernels (SEMI and
+ *   ANTI even over duplicate inner keys: "slot not empty" is the whole answer); everything else
+ *   the general kernel.
  * ------------------------------------------------------------------ */
 typedef struct strom_hashjoin_table strom_hashjoin_table;
 
@@ -429,14 +445,16 @@ strom_task *strom_submit_gpuhashjoin(strom_hashjoin_table *tbl,
  * kern_data_store whose head (ncols, colmeta, nrooms) the caller filled;
  * destination column r takes column src_colidx[r] (0-based) of relation
  * src_depth[r] (0 = outer chunk, d = d-th inner relation).  On completion
- * kds_dest holds nitems rows.  Fixed-width by-value columns.
+ * kds_dest holds nitems rows.  Fixed-width by-value columns.  A record whose
+ * slot for the relation is 0 ("no entry", see above): isnull is set, the value 0.
  * A kds_dest of KDS_FORMAT_ROW_FLAT takes kern_gpuhashjoin_projection_row
  * instead (opencl_hashjoin.h:437-689): the joined rows as heap tuples that
  * grow from the tail of the caller's buffer ('length' bytes in all; head with
  * ncols, colmeta {attlen, attalign}, nrooms, tdtypeid / tdtypmod filled by the
  * caller), row items behind the head, 'usage' = bytes of tuples.  Varlena
  * columns (attlen -1: text, character(n), numeric in its heap form) are
- * copied verbatim.  StromError_DataStoreNoSpace when the records outnumber
+ * copied verbatim.  Columns of a relation with "no entry" are NULL: the tuple
+ * carries a NULL bitmap (HEAP_HASNULL).  StromError_DataStoreNoSpace when the records outnumber
  * nrooms (kern_resultbuf.nitems says how many) or the tuples do not fit
  * 'length'; DataStoreCorruption when a destination column's attlen is not
  * its source's.
@@ -478,7 +496,11 @@ strom_task *strom_submit_gpuhashjoin_projection(strom_hashjoin_table *tbl,
  * TUPSLOT 'outer' as its source answers BadRequestMessage; a result beyond
  * 4 GB answers DataStoreOutOfRange.
  * Fixed-width inner columns of a single-relation table with a DIRECT index and
- * unique keys are served from slot-indexed arrays the table builds on first use.
+ * unique keys are served from slot-indexed arrays the table builds on first use
+ * -- of an INNER join only; a table whose program names another join type goes
+ * through the entries.  Columns of a relation with "no entry" (slot 0) are NULL
+ * in the bitmap and the zone maps; a NULL text datum has offset 0 and takes no
+ * heap bytes.
  * A join that ended with
  * StromError_DataStoreNoSpace is reported as such: resize, join again.
  */
@@ -498,8 +520,9 @@ strom_dstore *strom_hashjoin_project_column(strom_task *join_task, strom_hashjoi
  * type type_oids[r]; the session's program reads it as (var r+1 ...).
  * Needs one inner relation with a DIRECT index and unique keys, joined on a
  * plain outer column: inner columns then come from slot-indexed arrays the
- * table builds on first use.  Anything else answers BadRequest and the
- * caller goes through strom_hashjoin_project_column().
+ * table builds on first use.  Anything else -- a table whose program has a
+ * (jointype left | semi | anti) relation included -- answers BadRequest with
+ * nothing launched and the caller goes through strom_hashjoin_project_column().
  * Text / character(n): a variable of the program with one of these types
  * must be a column of 'outer' -- src_depth 0, type_oids STROM_TEXTOID /
  * STROM_BPCHARNOID as the variable's own type, onto a column with attlen
@@ -523,7 +546,9 @@ strom_task *strom_submit_gpupreagg_joined(strom_gpupreagg *sess, strom_task *joi
  * without a partner is dropped, virtual columns as above, a WHERE over
  * outer columns is the aggregate program's (qual ...).  Same requirements on
  * the table (one relation, DIRECT index, unique keys, key = a plain outer
- * column of int4 / int8 / date width); anything else answers BadRequest.
+ * column of int4 / int8 / date width, an INNER join: a table whose program
+ * names another join type is refused, here and by _lookup_star / _lookup_snowflake,
+ * with nothing launched); anything else answers BadRequest.
  * The JOIN program's own qual and parameters are NOT evaluated on this path
  * (only the aggregate program runs): a table whose program carries a
  * pulled-up outer qual or a join qual is refused with BadRequest -- put the
@@ -641,6 +666,15 @@ int strom_gpupreagg_lookup_snowflake_roots(int ntbls, const int32_t *parent, int
  * ------------------------------------------------------------------ */
 typedef struct strom_rowmap strom_rowmap;
 strom_rowmap *strom_rowmap_from_task(strom_task *gpuscan_task, int *p_errcode);
+/*
+ * ... and of a finished single-relation SEMI or ANTI GpuHashJoin submitted with
+ * STROM_RESULTS_ON_DEVICE: its records {outer_row + 1, 0} become a fresh kern_row_map of the outer
+ * chunk (out of place; the join's buffer stays the task's), each outer row at most once.  With
+ * the *_mapped calls this is "... FROM fact WHERE [NOT] EXISTS (...) GROUP BY ..." without a host
+ * round trip.  Any other join type, a table of several relations, a task that is no such join:
+ * BadRequest; a join that failed: its errcode (DataStoreNoSpace: resize, join again).
+ */
+strom_rowmap *strom_rowmap_from_join_task(strom_task *join_task, strom_hashjoin_table *tbl, int *p_errcode);
 uint32_t	strom_rowmap_nvalids(strom_rowmap *map);
 void	   *strom_rowmap_devptr(strom_rowmap *map);
 void		strom_rowmap_release(strom_rowmap *map);

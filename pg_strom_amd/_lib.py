@@ -186,6 +186,7 @@ PROTOTYPES = {
                                                        c_void_p, c_void_p, c_void_p, c_uint32,
                                                        c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "strom_rowmap_from_task": (c_void_p, [c_void_p, ctypes.POINTER(c_int)]),
+    "strom_rowmap_from_join_task": (c_void_p, [c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "strom_rowmap_nvalids": (c_uint32, [c_void_p]),
     "strom_rowmap_devptr": (c_void_p, [c_void_p]),
     "strom_rowmap_release": (None, [c_void_p]),

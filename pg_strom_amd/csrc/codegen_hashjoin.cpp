@@ -11,10 +11,21 @@
  * (strom_hashjoin.h) instead of CRC32 + the host-built slot array.
  *
  * IR:  (gpuhashjoin (rel (hashkey OUTER-EXPR INNER-ATTNO TYPE) ...
- *                        [(qual BOOL-EXPR)]) ...)
+ *                        [(qual BOOL-EXPR)]
+ *                        [(jointype inner|left|semi|anti)]) ...)
  * OUTER-EXPR / quals may use (var attno type) of the outer chunk and
  * (ivar depth attno type) of an inner relation already matched (for quals
  * also the current depth).
+ *
+ * The join type belongs to the inner relation (default: inner).  A prefix is the outer row plus
+ * what the earlier depths contributed; its candidates are the entries whose keys are equal and
+ * for which the qual -- the ON clause -- is true.
+ *   inner  the prefix goes on once per candidate; the record holds the entry's offset
+ *   left   ... and once with "no entry" (offset 0, every (ivar ..) of the depth NULL) if there is none
+ *   semi   once if there is a candidate, else not at all; the record holds 0
+ *   anti   once if there is none (NOT EXISTS: a NULL key has no candidate), else not at all; 0
+ * A semi / anti relation exposes no columns: only its own qual may read its (ivar ..).  RIGHT and
+ * FULL joins need "entry was matched" flags that outlive a chunk; they are refused by name.
  */
 #include <cstring>
 #include <cstdio>
@@ -30,6 +41,9 @@ using namespace strom;
 
 namespace {
 
+/* the values of HASHJOIN_JOIN_TYPE_<d> and HASHJOIN_FAST_JOINTYPE */
+enum { JOIN_INNER = 0, JOIN_LEFT = 1, JOIN_SEMI = 2, JOIN_ANTI = 3 };
+
 struct hashkey {
 	std::string	outer_text;
 	int			inner_attno;
@@ -42,7 +56,25 @@ struct rel {
 	std::string	qual_text;		/* empty: none */
 	std::set<std::pair<int,int>> ivars;	/* (attno, type) of this depth used anywhere */
 	std::set<std::pair<int,int>> expr_ivars;	/* ... used by an expression (not only as a key column) */
+	int			jointype = JOIN_INNER;
 };
+
+/* (ivar D ..) of a semi / anti relation D anywhere in an expression of a deeper relation? */
+void
+refuse_hidden_ivars(const sexpr &e, const std::vector<rel> &rels, int depth)
+{
+	if (!e.is_list)
+		return;
+	if (e.items.size() >= 2 && !e.items[0].is_list && e.items[0].atom == "ivar" && !e.items[1].is_list)
+	{
+		int		d = atoi(e.items[1].atom.c_str());
+		if (d >= 1 && d < depth && d <= (int)rels.size() &&
+			(rels[d - 1].jointype == JOIN_SEMI || rels[d - 1].jointype == JOIN_ANTI))
+			codegen_error("(ivar %d ..) at depth %d: a semi/anti relation exposes no columns", d, depth);
+	}
+	for (auto &it : e.items)
+		refuse_hidden_ivars(it, rels, depth);
+}
 
 /*
  * The 64-bit image of a key value the probe index hashes (and, in its DIRECT / KEYED forms,
@@ -97,6 +129,7 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 			if (!r.is_list || r.items.empty() || r.items[0].is_list || r.items[0].atom != "rel")
 				codegen_error("(rel ...) expected");
 			rel R;
+			bool have_jointype = false;
 			int depth = (int)rels.size() + 1;
 			ctx.ivar_max_depth = depth - 1;		/* keys may look at earlier depths only */
 			for (size_t j = 1; j < r.items.size(); j++)
@@ -113,6 +146,7 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 					if (!t)
 						codegen_error("unknown hashkey type %s", it.items[3].atom.c_str());
 					ctx.ivar_max_depth = depth - 1;
+					refuse_hidden_ivars(it.items[1], rels, depth);
 					int ot = codegen_expression(it.items[1], ctx, k.outer_text);
 					if (ot != t->type_oid)
 						codegen_error("hashkey: outer expression is %s but inner column is %s "
@@ -138,8 +172,31 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 					if (it.items.size() != 2)
 						codegen_error("(qual EXPR) expected");
 					ctx.ivar_max_depth = depth;
+					refuse_hidden_ivars(it.items[1], rels, depth);
 					if (codegen_expression(it.items[1], ctx, R.qual_text) != STROM_BOOLOID)
 						codegen_error("join qual is not boolean");
+				}
+				else if (it.items[0].atom == "jointype")
+				{
+					if (it.items.size() != 2 || it.items[1].is_list)
+						codegen_error("(jointype inner|left|semi|anti) expected");
+					if (have_jointype)
+						codegen_error("duplicate jointype item in rel %d", depth);
+					have_jointype = true;
+					const std::string &jt = it.items[1].atom;
+					if (jt == "inner")
+						R.jointype = JOIN_INNER;
+					else if (jt == "left")
+						R.jointype = JOIN_LEFT;
+					else if (jt == "semi")
+						R.jointype = JOIN_SEMI;
+					else if (jt == "anti")
+						R.jointype = JOIN_ANTI;
+					else if (jt == "right" || jt == "full")
+						codegen_error("jointype %s is not supported: right and full joins need "
+									  "entry-was-matched flags that outlive a chunk", jt.c_str());
+					else
+						codegen_error("unknown jointype %s", jt.c_str());
 				}
 				else
 					codegen_error("unknown rel item %s", it.items[0].atom.c_str());
@@ -163,7 +220,7 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 				R.ivars.insert({k.inner_attno, k.type_oid});
 
 		int		nrels = (int)rels.size();
-		char	tmp[1024];
+		char	tmp[4096];
 		std::string src = "/* generated by strom_codegen_gpuhashjoin */\n";
 		src += codegen_includes(ctx.extra_flags);
 		src += codegen_param_list(ctx);
@@ -173,9 +230,30 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 		/* fast path: one relation, one integer-like key, nothing else to test */
 		/* (a qual that reads outer columns only -- a scan's WHERE pulled up into
 		 * the join -- rides along: HASHJOIN_FAST_OUTER_QUAL) */
-		bool	fast = (nrels == 1 && rels[0].keys.size() == 1 &&
-						type_is_intlike(rels[0].keys[0].type_oid) && ctx.used_ivars.empty());
+		bool	all_inner = true;
+		for (auto &R : rels)
+			all_inner = all_inner && (R.jointype == JOIN_INNER);
+		bool	fast_shape = (nrels == 1 && rels[0].keys.size() == 1 &&
+							  type_is_intlike(rels[0].keys[0].type_oid) && ctx.used_ivars.empty());
+		bool	fast = (fast_shape && all_inner);
 		bool	fast_qual = (fast && !rels[0].qual_text.empty());
+		/*
+		 * The one-pass kernels serve a LEFT / SEMI / ANTI join of that shape too, WITHOUT a qual: a row
+		 * the ON clause rejects must be emitted under LEFT and ANTI, so the pulled-up-qual rule above
+		 * ("errors count for rows that found their entry") has nothing to say about it.  Every
+		 * consumer that reads records as "slot of a dimension row" is gated on HASHJOIN_FAST_ELIGIBLE,
+		 * which stays an all-inner property.
+		 */
+		int		fast_jointype = (fast_shape && !all_inner && rels[0].qual_text.empty()
+								 ? rels[0].jointype : 0);
+		for (int d = 1; d <= nrels; d++)
+		{
+			snprintf(tmp, sizeof(tmp), "#define HASHJOIN_JOIN_TYPE_%d %d\n", d, rels[d - 1].jointype);
+			src += tmp;
+		}
+		snprintf(tmp, sizeof(tmp), "#define HASHJOIN_ALL_INNER %d\n#define HASHJOIN_FAST_JOINTYPE %d\n",
+				 all_inner ? 1 : 0, fast_jointype);
+		src += tmp;
 		snprintf(tmp, sizeof(tmp), "#define HASHJOIN_FAST_ELIGIBLE %d\n#define HASHJOIN_FAST_OUTER_QUAL %d\n",
 				 fast ? 1 : 0, fast_qual ? 1 : 0);
 		src += tmp;
@@ -226,7 +304,7 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 		src += "  }\n  (void)errcode;\n  return false;\n}\n";
 
 		/* ---- outer key of the fast path -------------------------------- */
-		if (fast)
+		if (fast || fast_jointype != 0)
 		{
 			const char *tn = devtype_lookup(rels[0].keys[0].type_oid)->dev_name;
 			src += std::string("STROM_DEVICE bool\n"
@@ -269,10 +347,27 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 				snprintf(tmp, sizeof(tmp), "%s!okey_%d_%zu.isnull", k ? " && " : "", d, k);
 				allnotnull += tmp;
 			}
+			/*
+			 * LEFT and ANTI: the same chain walk with ONE extra trailing iteration ("no entry": off_<d> = 0,
+			 * every IVAR_<d>_* NULL) that runs when no candidate was found -- not a second copy of the
+			 * deeper nest, which would double the program text per such relation.  A NULL outer key has
+			 * no candidate, so the walk starts at its end.
+			 */
+			const bool	tailed = (R.jointype == JOIN_LEFT || R.jointype == JOIN_ANTI);
+			const std::string outer_indent = indent;
+			if (tailed)
+			{
+				snprintf(tmp, sizeof(tmp), "%scl_ulong kimg_%d[%zu];\n%scl_uint hash_%d = 0;\n%scl_uint off_%d = 0;\n",
+						 indent.c_str(), d, R.keys.size(), indent.c_str(), d, indent.c_str(), d);
+				src += tmp;
+			}
 			src += indent + "if (" + allnotnull + ")\n" + indent + "{\n";
 			indent += "  ";
-			snprintf(tmp, sizeof(tmp), "%scl_ulong kimg_%d[%zu];\n", indent.c_str(), d, R.keys.size());
-			src += tmp;
+			if (!tailed)
+			{
+				snprintf(tmp, sizeof(tmp), "%scl_ulong kimg_%d[%zu];\n", indent.c_str(), d, R.keys.size());
+				src += tmp;
+			}
 			for (size_t k = 0; k < R.keys.size(); k++)
 			{
 				char	oval[48];
@@ -290,6 +385,41 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 			/* ... and so does a KEYED index (one key of any type: a slot per distinct
 			 * key image, found by comparing images inside the 16-byte slot) */
 			bool	direct_ok = (R.keys.size() == 1 && image_is_exact(R.keys[0].type_oid));
+			if (tailed)
+			{
+				snprintf(tmp, sizeof(tmp), "%soff_%d = hashjoin_first(hjidx, %d, kimg_%d, %zu, &hash_%d);\n%s}\n",
+						 indent.c_str(), d, d - 1, d, R.keys.size(), d, outer_indent.c_str());
+				src += tmp;
+				indent = outer_indent;
+				snprintf(tmp, sizeof(tmp),
+						 "%sconst bool direct_%d = %s;\n"
+						 "%sconst bool single_%d = ALL_SINGLE || (direct_%d && hjidx->rel[%d].unique != 0);\n"
+						 "%sbool hit_%d = false;\n"
+						 "%sfor (cl_uint next_%d = 0, tail_%d = 0; ; off_%d = next_%d)\n%s{\n"
+						 "%s  if (off_%d == 0)\n%s  {\n"
+						 "%s    if (tail_%d != 0 || hit_%d)\n%s      break;\n"
+						 "%s    tail_%d = 1;\n%s  }\n",
+						 indent.c_str(), d,
+						 direct_ok ? ("(ALL_SINGLE || hjidx->rel[" + std::to_string(d - 1) + "].mode != HASHJOIN_MODE_HASH)").c_str() : "false",
+						 indent.c_str(), d, d, d - 1,
+						 indent.c_str(), d,
+						 indent.c_str(), d, d, d, d, indent.c_str(),
+						 indent.c_str(), d, indent.c_str(),
+						 indent.c_str(), d, d, indent.c_str(),
+						 indent.c_str(), d, indent.c_str());
+				src += tmp;
+				indent += "  ";
+				snprintf(tmp, sizeof(tmp),
+						 "%sconst kern_hashentry *ent_%d = (const kern_hashentry *)((const char *)kht_%d + off_%d);\n"
+						 "%snext_%d = ((tail_%d != 0 || single_%d) ? 0 : ent_%d->next);\n"
+						 "%sif (tail_%d == 0 && !direct_%d && ent_%d->hash != hash_%d)\n%s  continue;\n",
+						 indent.c_str(), d, d, d,
+						 indent.c_str(), d, d, d, d,
+						 indent.c_str(), d, d, d, d, indent.c_str());
+				src += tmp;
+			}
+			else
+			{
 			snprintf(tmp, sizeof(tmp),
 					 "%scl_uint hash_%d;\n"
 					 "%sconst bool direct_%d = %s;\n"
@@ -314,16 +444,31 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 					 indent.c_str(), d, d, d,
 					 indent.c_str(), d, d, d, indent.c_str());
 			src += tmp;
+			}
 			/* inner columns an expression refers to are fetched here; columns
 			 * that only serve the key comparison inside its branch */
 			for (auto &iv : R.expr_ivars)
 			{
 				const char *tn = devtype_lookup(iv.second)->dev_name;
+				if (tailed)
+					snprintf(tmp, sizeof(tmp),
+							 "%spg_%s_t IVAR_%d_%d;\n"
+							 "%sif (tail_%d != 0)\n%s{\n%s  IVAR_%d_%d.isnull = true;\n%s  IVAR_%d_%d.value = 0;\n%s}\n"
+							 "%selse\n%s  IVAR_%d_%d = pg_%s_tupref(errcode, kht_%d->colmeta, &ent_%d->htup, %d);\n",
+							 indent.c_str(), tn, d, iv.first,
+							 indent.c_str(), d, indent.c_str(), indent.c_str(), d, iv.first,
+							 indent.c_str(), d, iv.first, indent.c_str(),
+							 indent.c_str(), indent.c_str(), d, iv.first, tn, d, d, iv.first - 1);
+				else
 				snprintf(tmp, sizeof(tmp),
 						 "%spg_%s_t IVAR_%d_%d = pg_%s_tupref(errcode, kht_%d->colmeta, &ent_%d->htup, %d);\n",
 						 indent.c_str(), tn, d, iv.first, tn, d, d, iv.first - 1);
 				src += tmp;
 			}
+			if (tailed)
+				snprintf(tmp, sizeof(tmp), "%sbool keys_equal_%d = true;\n%sif (tail_%d == 0 && !direct_%d)\n%s{\n",
+						 indent.c_str(), d, indent.c_str(), d, d, indent.c_str());
+			else
 			snprintf(tmp, sizeof(tmp), "%sbool keys_equal_%d = true;\n%sif (!direct_%d)\n%s{\n",
 					 indent.c_str(), d, indent.c_str(), d, indent.c_str());
 			src += tmp;
@@ -362,15 +507,39 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 			std::string cond = "keys_equal_" + std::to_string(d);
 			if (!R.qual_text.empty())
 				cond += " && EVAL(" + R.qual_text + ")";
-			src += indent + "if (" + cond + ")\n" + indent + "{\n";
-			indent += "  ";
-			closing += "}\n}\n}\n";		/* if (cond), for, if (keys not null) */
+			if (tailed)
+			{
+				const std::string ds = std::to_string(d);
+				src += indent + "const bool cand_" + ds + " = (tail_" + ds + " == 0 && " + cond + ");\n";
+				if (R.jointype == JOIN_LEFT)
+					src += indent + "if (cand_" + ds + ")\n" + indent + "  hit_" + ds + " = true;\n" +
+						indent + "if (cand_" + ds + " || tail_" + ds + " != 0)\n" + indent + "{\n";
+				else	/* ANTI: one candidate settles it, the walk ends */
+					src += indent + "if (cand_" + ds + ")\n" + indent + "{\n" +
+						indent + "  hit_" + ds + " = true;\n" + indent + "  next_" + ds + " = 0;\n" + indent + "}\n" +
+						indent + "if (tail_" + ds + " != 0)\n" + indent + "{\n";
+				indent += "  ";
+				closing = "}\n}\n" + closing;		/* if (..), for */
+			}
+			else
+			{
+				src += indent + "if (" + cond + ")\n" + indent + "{\n";
+				indent += "  ";
+				/* SEMI: the deeper nest ran once for the first candidate; leave the walk */
+				closing = std::string(R.jointype == JOIN_SEMI ? "break;\n" : "") +
+					"}\n}\n}\n" + closing;		/* if (cond), for, if (keys not null) */
+			}
 		}
 		/* innermost: emit one record */
 		src += indent + "if (rbuffer)\n" + indent + "{\n" +
 			indent + "  __builtin_nontemporal_store((cl_int)(kds_index + 1), &rbuffer[0]);\n";
 		for (int d = 1; d <= nrels; d++)
 		{
+			/* a semi / anti relation contributes no entry: 0, "no entry" */
+			if (rels[d - 1].jointype == JOIN_SEMI || rels[d - 1].jointype == JOIN_ANTI)
+				snprintf(tmp, sizeof(tmp), "%s  __builtin_nontemporal_store((cl_int)0, &rbuffer[%d]);\n",
+						 indent.c_str(), d);
+			else
 			snprintf(tmp, sizeof(tmp), "%s  __builtin_nontemporal_store((cl_int)off_%d, &rbuffer[%d]);\n",
 					 indent.c_str(), d, d);
 			src += tmp;
@@ -381,6 +550,9 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 		src += indent + "else if (first_match && n_matches == 0)\n" + indent + "{\n";
 		for (int d = 1; d <= nrels; d++)
 		{
+			if (rels[d - 1].jointype == JOIN_SEMI || rels[d - 1].jointype == JOIN_ANTI)
+				snprintf(tmp, sizeof(tmp), "%s  first_match[%d] = 0;\n", indent.c_str(), d - 1);
+			else
 			snprintf(tmp, sizeof(tmp), "%s  first_match[%d] = (cl_int)off_%d;\n", indent.c_str(), d - 1, d);
 			src += tmp;
 		}

@@ -783,6 +783,46 @@ struct hashjoin_column_tile {
  * 2 = KEYED index (sparse integer keys): the probe is the 16-byte slot search of
  * hashjoin_first(), one pass instead of the general kernel's count + emit,
  * 3 = DIRECT slots in their 3-byte form (hashjoin_index_rel.slots3_off) */
+/*
+ * HASHJOIN_FAST_JOINTYPE (generated; 0 = inner, 1 = left, 2 = semi, 3 = anti): a compile-time
+ * constant of the program.  Only the emit predicate and the second word of the pair differ:
+ *   inner  emit when match != 0                                        {row + 1, match}
+ *   semi   emit when match != 0                                        {row + 1, 0}
+ *   anti   emit an existing row that raised no error and has match == 0  {row + 1, 0}
+ *   left   emit every existing row that raised no error                {row + 1, match}
+ * "match != 0" asks only whether the slot is empty, so SEMI and ANTI need no unique keys (the host
+ * asks for them under LEFT alone).  A NULL key and a key outside [key_min, key_min + nslots) both
+ * leave match == 0.  Rows of the ragged last tile beyond nitems must never be emitted: that is what
+ * the row_ok bits are for.  The inner instantiation is the code it was.
+ */
+#ifndef HASHJOIN_FAST_JOINTYPE
+#define HASHJOIN_FAST_JOINTYPE	0
+#endif
+#define HASHJOIN_JOIN_INNER		0
+#define HASHJOIN_JOIN_LEFT		1
+#define HASHJOIN_JOIN_SEMI		2
+#define HASHJOIN_JOIN_ANTI		3
+#if HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_LEFT || HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_ANTI
+#define HASHJOIN_FAST_ROW_OK	1
+#else
+#define HASHJOIN_FAST_ROW_OK	0
+#endif
+#if HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_LEFT
+#define HASHJOIN_FAST_EMITS(k,j)	(((row_ok[k] >> (j)) & 1) != 0)
+#elif HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_ANTI
+#define HASHJOIN_FAST_EMITS(k,j)	((((row_ok[k] >> (j)) & 1) != 0) && match[k][j] == 0)
+#else
+#define HASHJOIN_FAST_EMITS(k,j)	(match[k][j] != 0)
+#endif
+#if HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_SEMI || HASHJOIN_FAST_JOINTYPE == HASHJOIN_JOIN_ANTI
+#define HASHJOIN_FAST_WORD1(k,j)	0
+#else
+#define HASHJOIN_FAST_WORD1(k,j)	((cl_int)match[k][j])
+#endif
+#if HASHJOIN_FAST_JOINTYPE != 0 && HASHJOIN_FAST_OUTER_QUAL
+#error "the one-pass kernels take a non-inner join without a qual only"
+#endif
+
 template <int LDS_SLOTS, int QUADS>
 __device__ __forceinline__ void
 gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
@@ -844,6 +884,9 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 #if HASHJOIN_FAST_OUTER_QUAL
 		cl_int		qual_error[QUADS][4];
 #endif
+#if HASHJOIN_FAST_ROW_OK
+		cl_uint		row_ok[QUADS];		/* bit j: the row exists and raised no error */
+#endif
 
 		if (full_tile && !any_nulls)
 		{
@@ -892,6 +935,9 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 		for (int k = 0; k < QUADS; k++)
 		{
 			cl_uint	row0 = tile_base + (k * HASHJOIN_BLOCK + threadIdx.x) * 4;
+#if HASHJOIN_FAST_ROW_OK
+			row_ok[k] = 0;
+#endif
 #pragma unroll
 			for (int j = 0; j < 4; j++)
 			{
@@ -943,6 +989,10 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 					STROM_SET_ERROR(&chunk_error, errcode);
 					match[k][j] = 0;
 				}
+#if HASHJOIN_FAST_ROW_OK
+				else if (row0 + j < nitems)
+					row_ok[k] |= (1u << j);
+#endif
 			}
 		}
 #if HASHJOIN_FAST_OUTER_QUAL
@@ -963,6 +1013,9 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 		const int	GQ = HASHJOIN_APPEND_QUADS(QUADS);
 		static_assert(HASHJOIN_APPEND_QUADS(QUADS) >= 1 && QUADS % HASHJOIN_APPEND_QUADS(QUADS) == 0,
 					  "the LDS stage takes whole groups of quads");
+		/* LEFT (and ANTI without partners) emits EVERY row of a group: a group must fit an empty stage */
+		static_assert(HASHJOIN_APPEND_QUADS(QUADS) * HASHJOIN_BLOCK * 4 <= HASHJOIN_STAGE_ENTRIES,
+					  "a group of quads in which every row emits fits the stage");
 #pragma unroll
 		for (int g0 = 0; g0 < QUADS; g0 += GQ)
 		{
@@ -1000,7 +1053,7 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 #pragma unroll
 			for (int j = 0; j < 4; j++)
 			{
-				strom_lanemask_t m = __ballot(match[k][j] != 0);
+				strom_lanemask_t m = __ballot(HASHJOIN_FAST_EMITS(k, j));
 				prefix += strom_mbcnt(m);
 				total += __popcll(m);
 			}
@@ -1026,10 +1079,10 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 #pragma unroll
 			for (int j = 0; j < 4; j++)
 			{
-				if (match[k][j] != 0)
+				if (HASHJOIN_FAST_EMITS(k, j))
 				{
 					stage.entries[pos][0] = (cl_int)(row0 + j + 1);
-					stage.entries[pos][1] = (cl_int)match[k][j];
+					stage.entries[pos][1] = HASHJOIN_FAST_WORD1(k, j);
 					pos++;
 				}
 			}
@@ -1160,8 +1213,13 @@ gpuhashjoin_projection_slot(kern_hashjoin *khashjoin,
 			else if (depth > 0 && depth < (cl_int)nrels)
 			{
 				const kern_hashtable *kht = KERN_HASHTABLE(kmhash, depth - 1);
-				const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + rbuffer[depth]);
-				addr = kern_get_datum_tuple(kht->colmeta, &ent->htup, col);
+				/* offset 0 is the table head, never an entry: "no entry" (LEFT without a partner,
+				 * SEMI / ANTI), the column is NULL and the table is not read */
+				if (rbuffer[depth] != 0)
+				{
+					const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + rbuffer[depth]);
+					addr = kern_get_datum_tuple(kht->colmeta, &ent->htup, col);
+				}
 				attlen = (col < (cl_int)kht->ncols ? kht->colmeta[col].attlen : 0);
 			}
 			Datum	d = 0;
@@ -1214,7 +1272,8 @@ hashjoin_projection_locate(const kern_multihash *kmhash, const kern_data_store *
 	{
 		const kern_hashtable *kht = KERN_HASHTABLE(kmhash, depth - 1);
 		const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + rbuffer[depth]);
-		if (col >= 0 && col < (cl_int)kht->ncols)
+		/* offset 0: "no entry" -- the column is NULL, the table head is not read as an entry */
+		if (rbuffer[depth] != 0 && col >= 0 && col < (cl_int)kht->ncols)
 		{
 			s.addr = kern_get_datum_tuple(kht->colmeta, &ent->htup, col);
 			s.attlen = kht->colmeta[col].attlen;
@@ -1884,8 +1943,12 @@ hashjoin_proj_text_datum(const hashjoin_proj_textsrc &ts, const kern_data_store 
 		addr = (const char *)kern_get_datum(kds, ktoast, ts.col, outer_row);
 	else if (ts.kind == 3)
 	{
-		const kern_hashentry *ent = (const kern_hashentry *)((const char *)ts.kht + rbuf[ts.depth]);
-		addr = kern_get_datum_tuple(ts.kht->colmeta, &ent->htup, ts.col);
+		/* offset 0: "no entry" -- NULL, no heap bytes, and the table head is not read as an entry */
+		if (rbuf[ts.depth] != 0)
+		{
+			const kern_hashentry *ent = (const kern_hashentry *)((const char *)ts.kht + rbuf[ts.depth]);
+			addr = kern_get_datum_tuple(ts.kht->colmeta, &ent->htup, ts.col);
+		}
 	}
 	else
 		*p_bad = true;
@@ -2247,7 +2310,8 @@ gpuhashjoin_projection_column_body(kern_hashjoin *khashjoin,
 					const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + rbuf[k][depth]);
 					const HeapTupleHeaderData *htup = &ent->htup;
 					addr[k] = NULL;
-					if (valid[k] && !mismatch)
+					/* offset 0: "no entry" (a LEFT join's row without a partner) -- NULL, nothing read */
+					if (valid[k] && !mismatch && rbuf[k][depth] != 0)
 					{
 						cl_uint		hw = strom_fetch<cl_uint>((const char *)htup
 															  + offsetof(HeapTupleHeaderData, t_infomask2));

@@ -36,4 +36,43 @@ rowmap_from_results(kern_resultbuf *kresults, cl_uint nitems, cl_int *status)
 		*(cl_int *)((char *)kresults + offsetof(kern_resultbuf, results) - sizeof(cl_int)) = (cl_int)nitems;
 }
 
+/*
+ * A finished single-relation SEMI or ANTI GpuHashJoin: records {outer_row + 1, 0}, each outer row
+ * at most once by construction.  OUT of place: a record is 8 bytes, a map entry 4, and compacting
+ * a stride-2 source into its own head would have one work-group overwrite records another has not
+ * read yet.  The record count and the chunk status are read here, from the join's own result head:
+ * a join that failed, ran out of room, or has more than one inner relation yields no map.
+ */
+extern "C" __global__ void
+__launch_bounds__(256)
+rowmap_from_join_results(const kern_resultbuf *kresults, cl_uint nitems, kern_row_map *krowmap, cl_int *status)
+{
+	const cl_int *results = kresults->results;
+	bool		bad = false;
+
+	if (kresults->errcode != StromError_Success || kresults->nrels != 2 ||
+		kresults->nitems != nitems || nitems > kresults->nrooms)
+	{
+		/* (uniform: every thread leaves) */
+		if (threadIdx.x == 0)
+			atomicMax(status, kresults->errcode != StromError_Success
+					  ? (cl_int)kresults->errcode : (cl_int)StromError_BadRequestMessage);
+		return;
+	}
+	for (cl_uint i = blockIdx.x * blockDim.x + threadIdx.x;
+		 i < nitems;
+		 i += gridDim.x * blockDim.x)
+	{
+		cl_int	v = results[2 * (size_t)i];
+		if (v <= 0)
+			bad = true;
+		else
+			krowmap->rindex[i] = v - 1;
+	}
+	if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0)
+		atomicMax(status, StromError_DataStoreCorruption);
+	if (blockIdx.x == 0 && threadIdx.x == 0)
+		krowmap->nvalids = (cl_int)nitems;
+}
+
 #endif	/* STROM_ROWMAP_DEVICE_H */

@@ -373,8 +373,18 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		task->stream = dev->streams[0];
 	else
 		task->stream = dev->streams[1 + dev->next_stream++ % (dev->streams.size() - 1)];
+	/*
+	 * The join type of a one-pass program (HASHJOIN_FAST_JOINTYPE: 0 inner, 1 left, 2 semi, 3 anti).
+	 * SEMI and ANTI ask "is the slot empty" and nothing else, so they take the one-pass kernel over
+	 * an index with duplicate keys too; INNER and LEFT write the slot into the record and need it
+	 * to name ONE entry.
+	 */
+	int		fast_jointype = 0;
+	if (const char *p = strstr(prog->source.c_str(), "#define HASHJOIN_FAST_JOINTYPE "))
+		fast_jointype = atoi(p + strlen("#define HASHJOIN_FAST_JOINTYPE "));
+	bool	need_unique = (fast_jointype != 2 && fast_jointype != 3);
 	bool	fast = (tbl->ntables == 1 && (tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT || tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED) &&
-					tbl->head.rel[0].unique &&
+					(tbl->head.rel[0].unique || !need_unique) &&
 					req.format == KDS_FORMAT_COLUMN && req.krowmap == nullptr && req.rowmap_dev == nullptr &&
 					!getenv("STROM_HASHJOIN_NO_FAST"));
 	bool	fast_keyed = (fast && tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED);	/* sparse integer keys: KEYED index */
@@ -390,7 +400,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 	/* a program that is not fast-eligible still exports the symbol; the
 	 * eligibility is baked into hashjoin_fast_outer_key() returning false,
 	 * so ask the generated code */
-	if (fn && !strstr(prog->source.c_str(), "#define HASHJOIN_FAST_ELIGIBLE 1"))
+	if (fn && fast_jointype == 0 && !strstr(prog->source.c_str(), "#define HASHJOIN_FAST_ELIGIBLE 1"))
 		fn = nullptr;
 	fast = (fn != nullptr);
 	/*
@@ -1386,7 +1396,10 @@ strom::hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, 
 }
 
 /* key_min / slot count of that table, and which outer column its program joins on
- * (0: the key is an expression) */
+ * (0: the key is an expression).  HASHJOIN_FAST_ELIGIBLE is an all-inner property: a table whose
+ * program names (jointype left | semi | anti) is refused here, and with it by every fused fold
+ * (strom_submit_gpupreagg_joined / _lookup / _lookup_star / _lookup_snowflake) -- a row without a
+ * partner is dropped there, which is an inner join's answer and no other's */
 int
 strom::hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 								  int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual)
@@ -1403,6 +1416,91 @@ strom::hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min,
 	if (p_has_outer_qual)
 		*p_has_outer_qual = (strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_OUTER_QUAL 1") != nullptr);
 	return 0;
+}
+
+/*
+ * A finished single-relation SEMI or ANTI join, submitted with STROM_RESULTS_ON_DEVICE, as a
+ * device-resident row map of the outer chunk (rowmap_from_join_results in strom_rowmap.h): what
+ * strom_submit_gpuscan_mapped / _gpuhashjoin_mapped / _gpupreagg_mapped take, so
+ * "... FROM fact WHERE [NOT] EXISTS (...) GROUP BY ..." never leaves HBM.  Any other join type and
+ * more than one relation answer BadRequest, a failed task its errcode.
+ */
+extern "C" strom_rowmap *
+strom_rowmap_from_join_task(strom_task *handle, strom_hashjoin_table *tbl, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = 0;
+	strom_task_impl *task = static_cast<strom_task_impl *>(handle);
+	if (!task || !tbl)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	task_wait_completed(task);
+	int		jointype = 0;
+	if (const char *p = strstr(tbl->prog->source.c_str(), "#define HASHJOIN_JOIN_TYPE_1 "))
+		jointype = atoi(p + strlen("#define HASHJOIN_JOIN_TYPE_1 "));
+	if (!task->res_is_join || !task->keep_main || task->errcode != 0 || !task->main_devptr ||
+		task->dev != tbl->dev || tbl->ntables != 1 || (jointype != 2 && jointype != 3))
+	{
+		/* not a finished one-relation SEMI / ANTI GpuHashJoin with STROM_RESULTS_ON_DEVICE */
+		*p_errcode = (task->errcode ? task->errcode : StromError_BadRequestMessage);
+		return nullptr;
+	}
+	Device *dev = task->dev;
+	static strom_devprog_key key = strom_get_devprog_key("#include \"strom_kds.h\"\n"
+														 "#include \"strom_common.h\"\n"
+														 "#include \"strom_rowmap.h\"\n", 0);
+	if (strom_lookup_device_program(key, 1) != STROM_DEVPROG_READY)
+	{
+		*p_errcode = StromError_ProgramBuildFailure;
+		return nullptr;
+	}
+	int		errcode = 0;
+	(void)hipSetDevice(dev->hip_id);
+	hipFunction_t fn = lookup_program(key)->get_function(dev, "rowmap_from_join_results", &errcode);
+	if (!fn)
+	{
+		*p_errcode = errcode;
+		return nullptr;
+	}
+	hipStream_t stream = dev->streams[0];
+	cl_uint		a_nitems = task->res_nitems;
+	size_t		map_len = offsetof(kern_row_map, rindex) + sizeof(cl_int) * std::max<size_t>(1, a_nitems);
+	char	   *d_map = (char *)dev->pool.alloc(STROMALIGN(map_len) + sizeof(cl_int));
+	if (!d_map)
+	{
+		*p_errcode = StromError_OutOfMemory;
+		return nullptr;
+	}
+	cl_int	   *d_status = (cl_int *)(d_map + STROMALIGN(map_len));
+	cl_int		h_status = 0;
+	void	   *a_kres = (char *)task->main_devptr + task->res_offset;
+	void	   *a_map = d_map;
+	void	   *a_status = d_status;
+	void	   *args[] = { &a_kres, &a_nitems, &a_map, &a_status };
+	unsigned	grid = (unsigned)std::max<size_t>(1, std::min<size_t>(((size_t)a_nitems + 255) / 256,
+																	  (size_t)dev->prop.multiProcessorCount * 8));
+	bool		ok = (hipMemsetAsync(d_status, 0, sizeof(cl_int), stream) == hipSuccess &&
+					  hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
+					  hipMemcpyAsync(&h_status, d_status, sizeof(cl_int), hipMemcpyDeviceToHost, stream) == hipSuccess &&
+					  hipStreamSynchronize(stream) == hipSuccess);
+	if (!ok || h_status != 0)
+	{
+		dev->pool.release(d_map);
+		*p_errcode = (!ok ? StromError_HipInternal : h_status);
+		return nullptr;
+	}
+	strom_rowmap *map = new strom_rowmap();
+	map->buffer = d_map;
+	map->devptr = d_map;
+	map->nvalids = a_nitems;
+	map->dindex = dev->dindex;
+	return map;
+	STROM_ABI_CATCH(nullptr, p_errcode)
 }
 
 /*

@@ -172,6 +172,18 @@ class GpuHashJoin(object):
                                  dtype=np.int32).reshape(nitems, self.nrels)
         return HashJoinResult(nitems, 0, recs, runtime.perfmon_dict(pfm))
 
+    def row_map(self, pending):
+        """the surviving outer rows of a single-relation SEMI / ANTI join submitted with
+        STROM_RESULTS_ON_DEVICE over a resident chunk, kept in HBM as a kern_row_map for the next
+        operator (strom_rowmap_from_join_task; GpuScan.scan_to_rowmap is the scan's form).  Call it
+        BEFORE collect(pending), which is still due.  Raises StromError: BadRequest (-7) for any
+        other join, the join's own errcode (DataStoreNoSpace: resize, submit again) if it failed."""
+        err = ctypes.c_int(0)
+        handle = lib.strom_rowmap_from_join_task(pending[0], self.table, ctypes.byref(err))
+        if not handle:
+            raise runtime.StromError(err.value, "strom_rowmap_from_join_task")
+        return runtime.DeviceRowMap(handle)
+
     def join_chunk(self, chunk, row_map=None, nrooms=None, flags=0):
         """one chunk, with the reference's resize-and-retry on DataStoreNoSpace"""
         res = self.collect(self.submit(chunk, nrooms=nrooms, row_map=row_map, flags=flags))

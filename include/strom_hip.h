@@ -409,8 +409,9 @@ strom_task *strom_submit_gpupreagg_chunk(strom_devprog_key key,
  *   A candidate is an entry whose keys are equal (a NULL never is) and for which the rel's qual
  *   -- the ON clause -- is true.  OFFSET 0 IS NEVER AN ENTRY: the table head sits there, so 0 in a
  *   record means "no entry" and every projection below makes the relation's columns NULL without
- *   reading the table.  RIGHT and FULL joins are out of scope: they need "entry was matched"
- *   flags that outlive a chunk; the code generator refuses them by name.  A one-relation LEFT /
+ *   reading the table.  RIGHT and FULL joins are out of scope of (jointype ..), which the code
+ *   generator refuses by name: they are an INNER / LEFT program plus (track_matches), see "RIGHT
+ *   and FULL joins" below.  A one-relation LEFT /
  *   SEMI / ANTI join on one integer-like key without a qual takes the one-pass kernels (SEMI and
  *   ANTI even over duplicate inner keys: "slot not empty" is the whole answer); everything else
  *   the general kernel.
@@ -508,6 +509,67 @@ strom_dstore *strom_hashjoin_project_column(strom_task *join_task, strom_hashjoi
 											strom_dstore *outer, int ncols,
 											const int32_t *src_depth, const int32_t *src_colidx,
 											const int32_t *type_oids, int *p_errcode);
+
+/*
+ * RIGHT and FULL joins (JOIN_RIGHT / JOIN_FULL of the reference's planner, which it never sends to
+ * the device).  The per-chunk program of a RIGHT join is exactly the INNER program, that of a FULL
+ * join exactly the LEFT program; what differs is a property of the table and one extra pass:
+ *     RIGHT = (jointype inner) + (track_matches) + the unmatched pass after the last chunk
+ *     FULL  = (jointype left)  + (track_matches) + the same
+ * (track_matches) is an item of the LAST (rel ..) of the program, inner or left (an unmatched
+ * entry becomes a row in which everything else is NULL: no deeper relation may join onto it).  A
+ * table made from such a program keeps one flag byte per 32-byte granule of that relation's
+ * kern_hashtable behind its probe index; every probe kernel flags the entries it accepts (keys equal,
+ * qual true, prefix reached the relation), by entry offset.  A chunk that ends with
+ * DataStoreNoSpace has flagged all its candidates (the retry flags them again); after any other
+ * errcode the flags are unspecified -- a subset of the chunk's candidates -- and the query fails.
+ * The kern_multihash of a TRACKED table must be one that strom_multihash_build() made (or one laid
+ * out like it: LONGALIGNed entries that do not overlap).  The flag byte of a granule records ONE
+ * entry start; an image with entries that overlap or lie closer than their own length would lose
+ * start marks, and with them rows of the unmatched pass, without an error.
+ *
+ * strom_submit_gpuhashjoin_unmatched: records {0, .., 0, entry offset} of nrels ints for every
+ *   entry of the tracked relation without a flag, NULL-key entries included.  WORD 0 == 0 MEANS "NO
+ *   OUTER ROW" (a join record holds row + 1 there).  'khashjoin' as for a join; DataStoreNoSpace
+ *   with nitems = the room a retry needs; honours STROM_RESULTS_ON_DEVICE.
+ * strom_submit_gpuhashjoin_unmatched_projection: the same into a TUPSLOT or ROW_FLAT kds_dest;
+ *   every column of depth 0 is NULL, no outer chunk is read.
+ * strom_hashjoin_project_column(task, tbl, NULL, ..) takes an unmatched task submitted with
+ *   STROM_RESULTS_ON_DEVICE -- and outer == NULL takes no other task.
+ * strom_hashjoin_table_tracked_depth: the tracked relation (1-based), 0 for a table without.
+ * strom_hashjoin_table_reset_matches: every entry unmatched again (a rescan).
+ * strom_hashjoin_table_matches_length / _fetch / _merge: the multi-GPU seam.  Every rank holds the
+ *   same table and sees a shard of the outer rows; an entry is unmatched only if it is unmatched
+ *   on all ranks, so one rank ORs the others' flag images in (_merge; 'len' must be _length, and
+ *   the image must be of a table over the same kern_multihash: every bit but "matched" is compared
+ *   with the table's own, BadRequestMessage and nothing merged otherwise) and runs the unmatched pass.
+ * Ordering: the unmatched calls, _reset_matches, _matches_fetch and _matches_merge synchronise the
+ *   device first, so they come after every join task of this table submitted before them, waited
+ *   for or not.  Join tasks submitted afterwards are the caller's business.
+ * BadRequestMessage, nothing launched: any of these on a table without tracking (_tracked_depth
+ *   and _matches_length answer 0); strom_submit_gpupreagg_lookup / _lookup_star / _lookup_snowflake
+ *   on a TRACKED table (they probe without running the join program and would leave every flag
+ *   clear); strom_submit_gpupreagg_joined stays allowed for the JOIN tasks of such a table -- the join
+ *   ran and flagged -- and refuses a task of the unmatched pass: its records name no outer row.
+ * Still out: a tracked relation that is not the last; tracked tables in the fused lookup folds; a
+ *   run on more than one GPU (two tables on one device stand in for two ranks).
+ */
+strom_task *strom_submit_gpuhashjoin_unmatched(strom_hashjoin_table *tbl, kern_hashjoin *khashjoin,
+											   uint32_t flags, strom_done_cb done, void *arg,
+											   int *p_errcode);
+strom_task *strom_submit_gpuhashjoin_unmatched_projection(strom_hashjoin_table *tbl,
+														  kern_hashjoin *khashjoin,
+														  kern_data_store *kds_dest,
+														  const int32_t *src_depth,
+														  const int32_t *src_colidx,
+														  uint32_t flags,
+														  strom_done_cb done, void *arg,
+														  int *p_errcode);
+int			strom_hashjoin_table_tracked_depth(strom_hashjoin_table *tbl);
+int			strom_hashjoin_table_reset_matches(strom_hashjoin_table *tbl);
+size_t		strom_hashjoin_table_matches_length(strom_hashjoin_table *tbl);
+int			strom_hashjoin_table_matches_fetch(strom_hashjoin_table *tbl, void *buf, size_t len);
+int			strom_hashjoin_table_matches_merge(strom_hashjoin_table *tbl, const void *buf, size_t len);
 
 /*
  * GpuPreAgg straight over a join's result pairs -- the projection fused into

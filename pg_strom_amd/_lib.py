@@ -180,6 +180,16 @@ PROTOTYPES = {
                                           ctypes.POINTER(c_uint32), ctypes.POINTER(c_int),
                                           ctypes.POINTER(c_uint32)]),
     "strom_hashjoin_table_download": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "strom_submit_gpuhashjoin_unmatched": (c_void_p, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+                                                      ctypes.POINTER(c_int)]),
+    "strom_submit_gpuhashjoin_unmatched_projection": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                 c_uint32, c_void_p, c_void_p,
+                                                                 ctypes.POINTER(c_int)]),
+    "strom_hashjoin_table_tracked_depth": (c_int, [c_void_p]),
+    "strom_hashjoin_table_reset_matches": (c_int, [c_void_p]),
+    "strom_hashjoin_table_matches_length": (c_size_t, [c_void_p]),
+    "strom_hashjoin_table_matches_fetch": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "strom_hashjoin_table_matches_merge": (c_int, [c_void_p, c_void_p, c_size_t]),
     "strom_submit_gpuhashjoin": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_uint32, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "strom_submit_gpuhashjoin_projection": (c_void_p, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -12,7 +12,8 @@
  *
  * IR:  (gpuhashjoin (rel (hashkey OUTER-EXPR INNER-ATTNO TYPE) ...
  *                        [(qual BOOL-EXPR)]
- *                        [(jointype inner|left|semi|anti)]) ...)
+ *                        [(jointype inner|left|semi|anti)]
+ *                        [(track_matches)]) ...)
  * OUTER-EXPR / quals may use (var attno type) of the outer chunk and
  * (ivar depth attno type) of an inner relation already matched (for quals
  * also the current depth).
@@ -25,7 +26,12 @@
  *   semi   once if there is a candidate, else not at all; the record holds 0
  *   anti   once if there is none (NOT EXISTS: a NULL key has no candidate), else not at all; 0
  * A semi / anti relation exposes no columns: only its own qual may read its (ivar ..).  RIGHT and
- * FULL joins need "entry was matched" flags that outlive a chunk; they are refused by name.
+ * FULL joins need "entry was matched" flags that outlive a chunk; as a jointype they are refused by
+ * name.  They are a property of the TABLE, not of the per-chunk program: (track_matches) on the LAST
+ * relation, inner (gives RIGHT) or left (gives FULL), makes the probe kernels flag every entry they
+ * accept (#define HASHJOIN_TRACK_DEPTH d; strom_hashjoin.h), and gpuhashjoin_unmatched emits the
+ * entries without a flag after the last chunk.  Only the last relation: an unmatched entry becomes a
+ * row in which everything else is NULL, which holds only if no deeper relation joins onto it.
  */
 #include <cstring>
 #include <cstdio>
@@ -57,6 +63,7 @@ struct rel {
 	std::set<std::pair<int,int>> ivars;	/* (attno, type) of this depth used anywhere */
 	std::set<std::pair<int,int>> expr_ivars;	/* ... used by an expression (not only as a key column) */
 	int			jointype = JOIN_INNER;
+	bool		track_matches = false;
 };
 
 /* (ivar D ..) of a semi / anti relation D anywhere in an expression of a deeper relation? */
@@ -194,9 +201,19 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 						R.jointype = JOIN_ANTI;
 					else if (jt == "right" || jt == "full")
 						codegen_error("jointype %s is not supported: right and full joins need "
-									  "entry-was-matched flags that outlive a chunk", jt.c_str());
+									  "entry-was-matched flags that outlive a chunk (hint: (jointype %s) with "
+									  "(track_matches) on the last relation, then the unmatched pass)",
+									  jt.c_str(), jt == "right" ? "inner" : "left");
 					else
 						codegen_error("unknown jointype %s", jt.c_str());
+				}
+				else if (it.items[0].atom == "track_matches")
+				{
+					if (it.items.size() != 1)
+						codegen_error("(track_matches) takes no argument");
+					if (R.track_matches)
+						codegen_error("duplicate track_matches item in rel %d", depth);
+					R.track_matches = true;
 				}
 				else
 					codegen_error("unknown rel item %s", it.items[0].atom.c_str());
@@ -209,6 +226,19 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 		}
 		if (rels.empty() || rels.size() > 8)
 			codegen_error("1..8 inner relations expected");
+		int		track_depth = 0;
+		for (size_t d = 1; d <= rels.size(); d++)
+		{
+			if (!rels[d - 1].track_matches)
+				continue;
+			if (d != rels.size())
+				codegen_error("track_matches on rel %zu: only the last relation (%zu) can be tracked -- "
+							  "a deeper relation would join onto its unmatched entries", d, rels.size());
+			if (rels[d - 1].jointype != JOIN_INNER && rels[d - 1].jointype != JOIN_LEFT)
+				codegen_error("track_matches on a %s relation: only inner (RIGHT join) and left (FULL join) "
+							  "relations expose entries", rels[d - 1].jointype == JOIN_SEMI ? "semi" : "anti");
+			track_depth = (int)d;
+		}
 		/* inner columns referenced through (ivar ..), plus every key column */
 		for (auto &iv : ctx.used_ivars)
 		{
@@ -227,6 +257,12 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 		src += codegen_var_list(ctx, "STROM_KVAR_LIST");
 		snprintf(tmp, sizeof(tmp), "#define HASHJOIN_NRELS %d\n", nrels);
 		src += tmp;
+		/* (only a program that tracks: every other program is the text it was) */
+		if (track_depth != 0)
+		{
+			snprintf(tmp, sizeof(tmp), "#define HASHJOIN_TRACK_DEPTH %d\n", track_depth);
+			src += tmp;
+		}
 		/* fast path: one relation, one integer-like key, nothing else to test */
 		/* (a qual that reads outer columns only -- a scan's WHERE pulled up into
 		 * the join -- rides along: HASHJOIN_FAST_OUTER_QUAL) */
@@ -529,6 +565,15 @@ strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int *p_nr
 				closing = std::string(R.jointype == JOIN_SEMI ? "break;\n" : "") +
 					"}\n}\n}\n" + closing;		/* if (cond), for, if (keys not null) */
 			}
+		}
+		/* innermost: the COUNT pass (it sees every row, the counting-only mode after DataStoreNoSpace
+		 * included; the emit pass may copy a row's only match and never walk to the entry) flags the
+		 * tracked relation's candidate; the "no entry" turn of a LEFT relation has none */
+		if (track_depth != 0)
+		{
+			snprintf(tmp, sizeof(tmp), "%sif (!rbuffer && off_%d != 0)\n%s  hashjoin_flag_matched(hjidx, off_%d);\n",
+					 indent.c_str(), track_depth, indent.c_str(), track_depth);
+			src += tmp;
 		}
 		/* innermost: emit one record */
 		src += indent + "if (rbuffer)\n" + indent + "{\n" +

@@ -366,7 +366,18 @@ struct hashjoin_index_rel {
 };
 struct hashjoin_index {
 	cl_uint		nrels;
-	cl_uint		__pad[3];
+	/*
+	 * RIGHT / FULL joins: the relation whose entries the probe kernels flag (0: none; it is the
+	 * program's HASHJOIN_TRACK_DEPTH) and its flag area behind the slot arrays: ONE BYTE per 32-byte
+	 * granule of that relation's kern_hashtable, addressed by (entry offset >> 5) -- an entry is at
+	 * least 40 bytes long, so at most one starts in a granule.  0x80: an entry starts here, at
+	 * 8 x (the low two bits) into the granule (set once, by the index build); 0x40: it was matched
+	 * (set by the probes, cleared by strom_hashjoin_table_reset_matches).  track_len is a multiple
+	 * of 16 (strom_hashjoin.h: HASHJOIN_FLAG_*).
+	 */
+	cl_uint		track_depth;
+	cl_uint		track_off;		/* bytes from the index base */
+	cl_uint		track_len;		/* bytes == granules covered */
 	hashjoin_index_rel rel[HASHJOIN_MAXRELS];
 };
 struct hashjoin_build_stats {

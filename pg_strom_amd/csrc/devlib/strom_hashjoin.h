@@ -175,6 +175,55 @@ hashjoin_candidate(const hashjoin_index *hjidx, int d0, const kern_hashentry *en
 	return hjidx->rel[d0].mode != HASHJOIN_MODE_HASH || ent->hash == hash;
 }
 
+#ifdef HASHJOIN_TRACK_DEPTH
+/*
+ * RIGHT / FULL joins: (track_matches) on the last relation (generated: HASHJOIN_TRACK_DEPTH; a
+ * program without it has none of this).  One flag byte per 32-byte granule of the tracked
+ * kern_hashtable (hashjoin_index.track_off, strom_ctl.h), addressed by the ENTRY OFFSET every kernel
+ * already holds: the 48-byte entry is not touched.  An entry is at least 40 bytes long (its head and
+ * a heap tuple header, LONGALIGNed), so at most ONE entry starts in a granule; the byte keeps where:
+ * HASHJOIN_FLAG_STARTS | ((offset >> 3) & 3).  That is stored once by the index build, for every
+ * entry the host-built chains reach (one with a NULL key included: it hangs off no probe chain and
+ * must be emitted all the same); a probe that accepts an entry stores the same with
+ * HASHJOIN_FLAG_MATCHED over it -- it knows the offset, so it knows the whole byte.
+ * (A byte per 8-byte granule was measured first: 6.6 MB of flags for 1e6 entries do not stay in an
+ * XCD's 4 MB L2 beside the slot array, and the one-pass probe went from 0.42 to 1.34 ms per 1e8 rows.)
+ *
+ * A byte, not a bit: a bit needs a read-modify-write, that is a device-scope atomicOr, and global
+ * atomics execute at the memory side as uncached 64-byte requests -- one scattered dword per lane is
+ * their slowest shape, and same-address atomics run at 30 - 40 M/s chip-wide.  A byte is written by a
+ * plain store of a constant: no update of a neighbouring flag can be lost, there is nothing to
+ * order, and the area stays in L2 like the slot arrays.
+ *
+ * Test before set: the flag is READ with a plain load and written only when it is not yet set --
+ * after the first chunk or two nearly every probe is a read that hits L2.  A stale read (another
+ * XCD's store is not visible yet) is harmless: flags only go from STARTS to STARTS | MATCHED, so it
+ * costs at most one redundant store of the same value.
+ */
+#define HASHJOIN_FLAG_SHIFT		5			/* 32-byte granules */
+#define HASHJOIN_FLAG_STARTS	0x80
+#define HASHJOIN_FLAG_MATCHED	0x40
+#define HASHJOIN_FLAG_POSITION	0x03		/* (offset >> 3) & 3: the LONGALIGNed position inside the granule */
+#define HASHJOIN_FLAG_OF(off)	((cl_uchar)(HASHJOIN_FLAG_STARTS | (((off) >> 3) & HASHJOIN_FLAG_POSITION)))
+static_assert(offsetof(kern_hashentry, htup) + HEAPTUPLE_HEADER_FIXED > (1u << HASHJOIN_FLAG_SHIFT),
+			  "no two entries start in one flag granule");
+
+STROM_DEVICE cl_uchar *
+hashjoin_track_flags(const hashjoin_index *hjidx)
+{
+	return (cl_uchar *)hjidx + hjidx->track_off;
+}
+
+STROM_DEVICE void
+hashjoin_flag_matched(const hashjoin_index *hjidx, cl_uint entry_off)
+{
+	cl_uchar   *flag = hashjoin_track_flags(hjidx) + (entry_off >> HASHJOIN_FLAG_SHIFT);
+
+	if (!(*flag & HASHJOIN_FLAG_MATCHED))
+		*flag = HASHJOIN_FLAG_OF(entry_off) | HASHJOIN_FLAG_MATCHED;
+}
+#endif
+
 /* generated */
 STROM_DEVICE bool
 hashjoin_inner_key_images(int depth, const kern_hashtable *kht, const kern_hashentry *ent,
@@ -327,6 +376,12 @@ hashjoin_build_index_kernel(kern_multihash *kmhash, int depth, hashjoin_index *h
 			if (off >= kht->length)
 				break;
 			next_old = ent->next;		/* read before the entry is re-linked */
+#ifdef HASHJOIN_TRACK_DEPTH
+			/* "an entry starts here": the host-built chains reach every entry, the probe index's do
+			 * not (NULL keys below), and nothing says that entries lie back to back */
+			if (depth == HASHJOIN_TRACK_DEPTH && (off >> HASHJOIN_FLAG_SHIFT) < hjidx->track_len)
+				hashjoin_track_flags(hjidx)[off >> HASHJOIN_FLAG_SHIFT] = HASHJOIN_FLAG_OF(off);
+#endif
 			if (!hashjoin_inner_key_images(depth, kht, ent, images))
 			{
 				ent->next = 0;			/* a NULL key can never join */
@@ -1010,6 +1065,36 @@ gpuhashjoin_main_fast_body(kern_hashjoin *khashjoin,
 			}
 		}
 #endif
+#if defined(HASHJOIN_TRACK_DEPTH) && HASHJOIN_NRELS == 1
+		/*
+		 * match[k][j] != 0 now means "this row joined that entry": a row that raised an error, one
+		 * the pulled-up qual's error zeroed and a ragged tile's row beyond nitems all hold 0.  The
+		 * tile's flag reads are issued together, behind its resolved slot reads, then the few stores
+		 * (test before set: hashjoin_flag_matched says why a stale read is harmless).
+		 */
+		{
+			cl_uchar   *track_flags = hashjoin_track_flags(hjidx);
+			cl_uchar	seen[QUADS][4];
+#pragma unroll
+			for (int k = 0; k < QUADS; k++)
+			{
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+					seen[k][j] = (match[k][j] != 0 ? track_flags[match[k][j] >> HASHJOIN_FLAG_SHIFT]
+								  : (cl_uchar)HASHJOIN_FLAG_MATCHED);
+			}
+#pragma unroll
+			for (int k = 0; k < QUADS; k++)
+			{
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+				{
+					if (!(seen[k][j] & HASHJOIN_FLAG_MATCHED))
+						track_flags[match[k][j] >> HASHJOIN_FLAG_SHIFT] = HASHJOIN_FLAG_OF(match[k][j]) | HASHJOIN_FLAG_MATCHED;
+				}
+			}
+		}
+#endif
 		const int	GQ = HASHJOIN_APPEND_QUADS(QUADS);
 		static_assert(HASHJOIN_APPEND_QUADS(QUADS) >= 1 && QUADS % HASHJOIN_APPEND_QUADS(QUADS) == 0,
 					  "the LDS stage takes whole groups of quads");
@@ -1156,6 +1241,160 @@ gpuhashjoin_main_fast_keyed(kern_hashjoin *khashjoin,
 	gpuhashjoin_main_fast_body<2, HASHJOIN_QUADS>(khashjoin, hjidx, kds);
 }
 
+#ifdef HASHJOIN_TRACK_DEPTH
+/* ====================================================================== *
+ * RIGHT / FULL joins, the pass after the last outer chunk: one record
+ * {0, 0, .., 0, entry offset} of nrels ints per entry of the tracked (last)
+ * relation that no probe flagged.  WORD 0 == 0 MEANS "NO OUTER ROW": a join
+ * record holds row + 1 there.  The flag area is streamed, 16 flags per
+ * thread and load; a flag byte with STARTS and without MATCHED is an unmatched
+ * entry at (its index << 5) + (its position bits << 3).  The offsets are compacted by a wave
+ * scan into the one-pass kernels' LDS stage (as 2 x HASHJOIN_STAGE offsets)
+ * and leave with one reservation per flush and coalesced stores.  Without
+ * room the kernel goes on counting: nitems ends as the room a retry needs.
+ * ====================================================================== */
+#define HASHJOIN_UNMATCHED_STAGE	(2 * HASHJOIN_STAGE_ENTRIES)		/* offsets */
+#define HASHJOIN_UNMATCHED_TILE		(HASHJOIN_BLOCK * 16)				/* flags */
+static_assert(HASHJOIN_UNMATCHED_TILE <= HASHJOIN_UNMATCHED_STAGE, "a tile of unmatched entries fits an empty stage");
+
+STROM_DEVICE void
+hashjoin_unmatched_flush(hashjoin_stage &stage, kern_resultbuf *kresults, cl_uint nwords_rec, cl_uint fill,
+						 cl_int *p_error)
+{
+	const cl_uint *staged = (const cl_uint *)stage.entries;
+
+	if (threadIdx.x == 0)
+		stage.flush_base = atomicAdd(&kresults->nitems, fill);
+	__syncthreads();
+	cl_uint		base = stage.flush_base;
+	if ((cl_ulong)base + fill <= (cl_ulong)kresults->nrooms)
+	{
+		cl_int	   *dest = kresults->results + (size_t)nwords_rec * base;
+		cl_uint		nwords = nwords_rec * fill;
+		for (cl_uint i = threadIdx.x; i < nwords; i += HASHJOIN_BLOCK)
+		{
+			cl_uint		rec = i / nwords_rec, w = i - rec * nwords_rec;
+			__builtin_nontemporal_store((cl_int)(w + 1 == nwords_rec ? staged[rec] : 0u), &dest[i]);
+		}
+	}
+	else
+		STROM_SET_ERROR(p_error, StromError_DataStoreNoSpace);
+	__syncthreads();
+}
+
+extern "C" __global__ void
+__launch_bounds__(HASHJOIN_BLOCK)
+gpuhashjoin_unmatched(kern_hashjoin *khashjoin, const hashjoin_index *hjidx)
+{
+	typedef cl_uint v4_t __attribute__((ext_vector_type(4)));
+	__shared__ hashjoin_stage stage;
+	kern_resultbuf *kresults = KERN_HASHJOIN_RESULTBUF(khashjoin);
+	cl_uint	   *staged = (cl_uint *)stage.entries;
+	const v4_t *flags = (const v4_t *)hashjoin_track_flags(hjidx);
+	const cl_uint nrels = kresults->nrels;				/* ints per record */
+	const cl_uint nvec = hjidx->track_len / 16;			/* (a multiple of 16 bytes, zero padded) */
+	const cl_uint ntiles = (nvec + HASHJOIN_BLOCK - 1) / HASHJOIN_BLOCK;
+	const cl_uint lane = threadIdx.x & (STROM_WAVE - 1);
+	const cl_uint wave = threadIdx.x / STROM_WAVE;
+	cl_int		chunk_error = StromError_Success;
+	cl_uint		fill = 0;
+
+	if (nrels != HASHJOIN_NRELS + 1 || hjidx->track_depth != HASHJOIN_TRACK_DEPTH)
+	{
+		if (threadIdx.x == 0)
+			atomicMax(&kresults->errcode, StromError_DataStoreCorruption);
+		return;
+	}
+	for (cl_uint tile = blockIdx.x; tile < ntiles; tile += gridDim.x)
+	{
+		cl_uint		vec = tile * HASHJOIN_BLOCK + threadIdx.x;
+		v4_t		f = (vec < nvec ? flags[vec] : (v4_t)(0u));
+		cl_uint		prefix = 0, total = 0;
+
+		/* bit b of 'mine': byte b of this thread's 16 flags is an unmatched entry */
+		cl_uint		mine = 0;
+#pragma unroll
+		for (int b = 0; b < 16; b++)
+		{
+			cl_uint		byte = (f[b >> 2] >> ((b & 3) * 8)) & 0xffu;
+			mine |= ((byte & (HASHJOIN_FLAG_STARTS | HASHJOIN_FLAG_MATCHED)) == HASHJOIN_FLAG_STARTS ? 1u << b : 0u);
+		}
+		/* lane-major inside the tile (a thread's up to 16 records lie together): this lane's position
+		 * is the count of the lower lanes, by a wave scan (one scan for the 16 flags, not a ballot each) */
+		{
+			cl_uint		cnt = __popc(mine), incl = cnt;
+#pragma unroll
+			for (int o = 1; o < STROM_WAVE; o <<= 1)
+			{
+				cl_uint	up = __shfl_up(incl, o, STROM_WAVE);
+				if ((int)lane >= o)
+					incl += up;
+			}
+			prefix = incl - cnt;
+			total = __shfl(incl, STROM_WAVE - 1, STROM_WAVE);
+		}
+		if (lane == 0)
+			stage.wave_total[0][wave] = total;
+		__syncthreads();
+		cl_uint		before = 0, all = 0;
+#pragma unroll
+		for (int w = 0; w < HASHJOIN_NWAVES; w++)
+		{
+			cl_uint	t = stage.wave_total[0][w];
+			before += (w < (int)wave ? t : 0);
+			all += t;
+		}
+		__syncthreads();						/* wave_total[] is rewritten by the next tile */
+		if (all == 0)
+			continue;							/* (uniform) */
+		if (fill + all > HASHJOIN_UNMATCHED_STAGE)
+		{
+			hashjoin_unmatched_flush(stage, kresults, nrels, fill, &chunk_error);
+			fill = 0;
+		}
+		cl_uint		pos = fill + before + prefix;
+#pragma unroll
+		for (int b = 0; b < 16; b++)
+		{
+			if ((mine >> b) & 1)
+			{
+				cl_uint		byte = (f[b >> 2] >> ((b & 3) * 8)) & 0xffu;
+				staged[pos++] = ((vec * 16 + b) << HASHJOIN_FLAG_SHIFT) | ((byte & HASHJOIN_FLAG_POSITION) << 3);
+			}
+		}
+		__syncthreads();
+		fill += all;
+	}
+	if (fill > 0)
+		hashjoin_unmatched_flush(stage, kresults, nrels, fill, &chunk_error);
+	{
+		cl_int worst = strom_wave_max_i32(chunk_error);
+		if (strom_lane_id() == 0 && worst != StromError_Success)
+			atomicMax(&kresults->errcode, worst);
+	}
+}
+
+/* the flag area as a whole, 4 flags a word: op 0 clears every "matched" bit (a rescan), op 1 ORs in
+ * the image of another rank's area over the same table (an entry is unmatched only if it is on
+ * every rank) */
+extern "C" __global__ void
+__launch_bounds__(256)
+hashjoin_matches_kernel(hashjoin_index *hjidx, const cl_uint *image, cl_int op)
+{
+	cl_uint	   *words = (cl_uint *)hashjoin_track_flags(hjidx);
+	cl_uint		nwords = hjidx->track_len / 4;
+
+	for (cl_uint i = blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += gridDim.x * blockDim.x)
+	{
+		cl_uint		w = words[i];
+		cl_uint		n = (op == 0 ? w & ~(0x01010101u * HASHJOIN_FLAG_MATCHED)
+						 : w | (image[i] & (0x01010101u * HASHJOIN_FLAG_MATCHED)));
+		if (n != w)
+			words[i] = n;
+	}
+}
+#endif	/* HASHJOIN_TRACK_DEPTH */
+
 /* ====================================================================== *
  * projection into a TUPSLOT kern_data_store
  * (kern_gpuhashjoin_projection_slot, opencl_hashjoin.h:691-839).  One
@@ -1205,7 +1444,12 @@ gpuhashjoin_projection_slot(kern_hashjoin *khashjoin,
 			const void *addr = NULL;
 			cl_int		attlen = 0;
 
-			if (depth == 0)
+			if (depth == 0 && (kds == NULL || rbuffer[0] == 0))
+			{
+				/* word 0 == 0: "no outer row" (an unmatched entry of a RIGHT / FULL join) -- every
+				 * outer column is NULL; no outer chunk is present, none is read */
+			}
+			else if (depth == 0)
 			{
 				addr = kern_get_datum(kds, ktoast, col, (cl_uint)(rbuffer[0] - 1));
 				attlen = (col < (cl_int)kds->ncols ? kds->colmeta[col].attlen : 0);
@@ -1260,7 +1504,11 @@ hashjoin_projection_locate(const kern_multihash *kmhash, const kern_data_store *
 	hashjoin_proj_src s;
 	s.addr = NULL;
 	s.attlen = 0;
-	if (depth == 0)
+	if (depth == 0 && (kds == NULL || rbuffer[0] == 0))
+	{
+		/* word 0 == 0: "no outer row" -- NULL; no outer chunk is present, none is read */
+	}
+	else if (depth == 0)
 	{
 		if (col >= 0 && col < (cl_int)kds->ncols)
 		{
@@ -1842,7 +2090,7 @@ hashjoin_dimrec_narrow_kernel(const hashjoin_dimrec_spec *spec, const char *recs
  */
 struct hashjoin_proj_textsrc {
 	cl_int		kind;			/* 0: nothing readable (the mapping does not fit), 1: COLUMN outer chunk,
-								 * 2: ROW / ROW_FLAT outer chunk, 3: inner relation */
+								 * 2: ROW / ROW_FLAT outer chunk, 3: inner relation, 4: no outer chunk */
 	cl_int		depth;
 	cl_int		col;
 	cl_uint		values_off;		/* kind 1 */
@@ -1862,7 +2110,9 @@ hashjoin_proj_text_source(const kern_data_store *kds, const kern_multihash *kmha
 	ts.values_off = 0;
 	ts.nulls_off = 0;
 	ts.kht = NULL;
-	if (depth == 0)
+	if (depth == 0 && kds == NULL)
+		ts.kind = 4;		/* the records of the unmatched pass: no outer chunk, every datum NULL */
+	else if (depth == 0)
 	{
 		/* a by-value source column is never followed as an address */
 		if (col < 0 || col >= (cl_int)kds->ncols || kds->colmeta[col].attlen >= 0)
@@ -1899,6 +2149,9 @@ hashjoin_proj_text_datum(const hashjoin_proj_textsrc &ts, const kern_data_store 
 	const char *addr = NULL;
 
 	*p_size = 0;
+	/* word 0 == 0: "no outer row" -- an outer datum is NULL (offset 0, no heap bytes), nothing is read */
+	if (ts.kind == 4 || (ts.depth == 0 && rbuf[0] == 0))
+		return NULL;
 	if (ts.kind == 1)
 	{
 		cl_ulong	length = kds->length;
@@ -2047,7 +2300,9 @@ gpuhashjoin_projection_column_body(kern_hashjoin *khashjoin,
 	cl_uint		nrels = kresults->nrels;
 	cl_uint		nitems = dst->nitems;				/* set by the host from the finished join */
 	cl_uint		ncols = dst->ncols;
-	bool		outer_is_column = (kds->format == KDS_FORMAT_COLUMN);
+	/* kds == NULL: the records of the unmatched pass (word 0 == 0, "no outer row"): every column of
+	 * depth 0 is NULL, no outer chunk is present and none is read */
+	bool		outer_is_column = (kds != NULL && kds->format == KDS_FORMAT_COLUMN);
 	cl_uint		lane = threadIdx.x & 63;
 
 	if (threadIdx.x == 0)
@@ -2256,6 +2511,13 @@ gpuhashjoin_projection_column_body(kern_hashjoin *khashjoin,
 				/* (per lane, unlike a width mismatch: one record's datum may be the unreadable one) */
 				if (mismatch)
 					col_has_null[ncols] = 1;
+			}
+			else if (depth == 0 && kds == NULL)
+			{
+				/* "no outer row": NULL in the bitmap, 0 in the array, out of the zone map */
+#pragma unroll
+				for (int k = 0; k < HASHJOIN_PROJ_ROWS; k++)
+					addr[k] = NULL;
 			}
 			else if (depth == 0 && s_src_values[r] != 0)
 			{

@@ -27,6 +27,7 @@ struct strom_hashjoin_table {
 	size_t				index_len = 0;
 	hashjoin_index			head;
 	int					ntables = 0;
+	int					track_depth = 0;		/* the program's HASHJOIN_TRACK_DEPTH: (track_matches), RIGHT / FULL joins */
 	cl_uint				rel_ncols[HASHJOIN_MAXRELS] = {};	/* columns of each inner relation (host-side request validation) */
 	std::atomic<int>	refcnt{1};
 	/* inner columns by slot for the COLUMN projection (DIRECT index, unique
@@ -118,7 +119,17 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 		*p_errcode = errcode;
 		return nullptr;
 	}
+	/* (track_matches): the program flags the entries of its LAST relation, which must be the table's */
+	int		track_depth = 0;
+	if (const char *p = strstr(prog->source.c_str(), "#define HASHJOIN_TRACK_DEPTH "))
+		track_depth = atoi(p + strlen("#define HASHJOIN_TRACK_DEPTH "));
+	if (track_depth != 0 && track_depth != (int)kmhash->ntables)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
 	std::unique_ptr<strom_hashjoin_table> tbl(new strom_hashjoin_table());
+	tbl->track_depth = track_depth;
 	static std::atomic<uint64_t> next_serial{1};
 	tbl->serial = next_serial++;
 	tbl->key = key;
@@ -222,6 +233,19 @@ strom_hashjoin_table_create(strom_devprog_key key, const kern_multihash *kmhash,
 			ir.slots3_off = (cl_uint)off;
 			off += STROM_TYPEALIGN(256, 3 * (size_t)ir.nslots + 16);
 		}
+	}
+	/* the flag area of the tracked relation (strom_ctl.h: track_off), zeroed with the rest of the index;
+	 * the build kernel below stores "an entry starts here" while it walks the host-built chains */
+	if (track_depth != 0)
+	{
+		size_t	granules = ((size_t)KERN_HASHTABLE(kmhash, track_depth - 1)->length + 31) / 32;	/* HASHJOIN_FLAG_SHIFT */
+		size_t	len = STROM_TYPEALIGN(16, granules);
+		if (off + len + 256 > 0xffffffffUL)
+			return fail(StromError_DataStoreOutOfRange);
+		tbl->head.track_depth = (cl_uint)track_depth;
+		tbl->head.track_off = (cl_uint)off;
+		tbl->head.track_len = (cl_uint)len;
+		off += STROM_TYPEALIGN(256, len);
 	}
 	tbl->index_len = off;
 	tbl->d_index = (char *)dev->pool.alloc(off);
@@ -349,6 +373,7 @@ struct hashjoin_request {
 	strom_dstore	   *kds_dev;
 	const kern_row_map *krowmap;
 	strom_rowmap	   *rowmap_dev = nullptr;	/* device-resident row map (chained operators) */
+	bool				unmatched = false;		/* the pass after the last chunk: no outer chunk at all */
 	uint32_t			flags;
 	uint32_t			format;
 	uint32_t			nrows;
@@ -383,7 +408,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 	if (const char *p = strstr(prog->source.c_str(), "#define HASHJOIN_FAST_JOINTYPE "))
 		fast_jointype = atoi(p + strlen("#define HASHJOIN_FAST_JOINTYPE "));
 	bool	need_unique = (fast_jointype != 2 && fast_jointype != 3);
-	bool	fast = (tbl->ntables == 1 && (tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT || tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED) &&
+	bool	fast = (!req.unmatched && tbl->ntables == 1 && (tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT || tbl->head.rel[0].mode == HASHJOIN_MODE_KEYED) &&
 					(tbl->head.rel[0].unique || !need_unique) &&
 					req.format == KDS_FORMAT_COLUMN && req.krowmap == nullptr && req.rowmap_dev == nullptr &&
 					!getenv("STROM_HASHJOIN_NO_FAST"));
@@ -432,7 +457,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		}
 	}
 	if (!fn)
-		fn = prog->get_function(dev, "gpuhashjoin_main", &errcode);
+		fn = prog->get_function(dev, req.unmatched ? "gpuhashjoin_unmatched" : "gpuhashjoin_main", &errcode);
 	if (!fn)
 	{
 		task_fail(task, errcode);
@@ -457,8 +482,10 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 							 hipMemcpyHostToDevice, task->stream), "send kern_hashjoin");
 	task->pfm.num_dma_send++;
 	task->pfm.bytes_dma_send += head_len;
-	const void *d_kds;
-	if (req.kds_dev)
+	const void *d_kds = nullptr;
+	if (req.unmatched)
+		;				/* every projection below takes "no outer chunk" */
+	else if (req.kds_dev)
 		d_kds = req.kds_dev->devptr;
 	else
 	{
@@ -516,6 +543,8 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 			: fast ? (size_t)block * 4 * fast_quads : (size_t)block;
 		size_t	ntiles = (req.nrows + tile_rows - 1) / tile_rows;
 		(void)generic_rows;
+		if (req.unmatched)
+			ntiles = ((size_t)tbl->head.track_len / 16 + block - 1) / block;	/* 16 flags per thread */
 		int		per_cu = 0;
 		if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, lds_slot_bytes) != hipSuccess ||
 			per_cu < 1)
@@ -525,7 +554,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		size_t	grid = std::max<size_t>(1, std::min<size_t>(ntiles, (size_t)dev->prop.multiProcessorCount * per_cu));
 		/* a cap on the work-groups of the main kernel, one-pass and general alike (tests: one
 		 * work-group walks many tiles of a small chunk); read per launch, no part of the program */
-		if (const char *v = getenv("STROM_HASHJOIN_MAX_GRID"))
+		if (const char *v = getenv(req.unmatched ? "STROM_HASHJOIN_UNMATCHED_MAX_GRID" : "STROM_HASHJOIN_MAX_GRID"))
 			grid = std::min<size_t>(grid, (size_t)std::max(1, atoi(v)));
 		void	   *a_khj = d_khj;
 		const void *a_km = tbl->d_kmhash;
@@ -539,7 +568,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		 * (no memory to spare) the emit pass probes again, as before.
 		 */
 		void	   *a_first = nullptr;
-		if (!fast && !getenv("STROM_HASHJOIN_NO_FIRST_MATCH"))
+		if (!fast && !req.unmatched && !getenv("STROM_HASHJOIN_NO_FIRST_MATCH"))
 		{
 			size_t	len = (size_t)req.nrows * (size_t)tbl->ntables * sizeof(cl_int);
 			if (len > 0 && len <= ((size_t)8 << 30))
@@ -551,8 +580,9 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 		}
 		void	   *args_fast[] = { &a_khj, &a_ix, &a_kds };
 		void	   *args_gen[] = { &a_khj, &a_km, &a_ix, &a_kds, &a_toast, &a_map, &a_first };
+		void	   *args_unmatched[] = { &a_khj, &a_ix };
 		REQ_CHECK(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, (unsigned)lds_slot_bytes,
-										task->stream, fast ? args_fast : args_gen, nullptr),
+										task->stream, req.unmatched ? args_unmatched : fast ? args_fast : args_gen, nullptr),
 				  "launch gpuhashjoin kernel");
 		task->pfm.num_kern_exec++;
 		if (lds_slot_bytes)
@@ -625,6 +655,7 @@ gpuhashjoin_launch(strom_task_impl *task, hashjoin_request req)
 	kern_data_store *kds_dest = req.kds_dest;
 	task->res_offset = res_offset;
 	task->res_is_join = true;
+	task->res_is_unmatched = req.unmatched;
 	task->finish = [kres_host, d_khj, res_offset, results_on_device, stage_res,
 					kds_dest, d_dest, dest_head, dest_stride](strom_task_impl *t)
 	{
@@ -846,6 +877,198 @@ strom_submit_gpuhashjoin_mapped(strom_hashjoin_table *tbl, kern_hashjoin *khashj
 								  nullptr, nullptr, nullptr, flags, done, arg, p_errcode);
 }
 
+/* ----------------------------------------------------------------------
+ * RIGHT / FULL joins: a table whose program carries (track_matches)
+ *
+ * Ordering.  The join tasks of a table run on several streams and flag entries as they go.  The
+ * unmatched pass, _reset_matches, _matches_fetch and _matches_merge begin with a DEVICE
+ * SYNCHRONISATION: every join kernel of this table submitted before the call -- its task waited for
+ * or not -- has then finished and its flags are in memory.  (Once per join, after the last chunk:
+ * events on the table would save nothing a query could notice.)  Join tasks submitted after the call
+ * are the caller's business.
+ * ---------------------------------------------------------------------- */
+static bool
+tracked_table_quiesce(strom_hashjoin_table *tbl)
+{
+	return (hipSetDevice(tbl->dev->hip_id) == hipSuccess && hipDeviceSynchronize() == hipSuccess);
+}
+
+extern "C" int
+strom_hashjoin_table_tracked_depth(strom_hashjoin_table *tbl)
+{
+	return (tbl ? tbl->track_depth : 0);
+}
+
+static strom_task *
+submit_unmatched_common(strom_hashjoin_table *tbl, kern_hashjoin *khashjoin,
+						kern_data_store *kds_dest, const int32_t *src_depth, const int32_t *src_colidx,
+						uint32_t flags, strom_done_cb done, void *arg, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	*p_errcode = 0;
+	if (!tbl || tbl->track_depth == 0 || !khashjoin)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	kern_resultbuf *kres = KERN_HASHJOIN_RESULTBUF(khashjoin);
+	if ((int)kres->nrels != tbl->ntables + 1)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	hashjoin_request req;
+	req.tbl = tbl;
+	req.khj = khashjoin;
+	req.kds = nullptr;
+	req.kds_dev = nullptr;
+	req.krowmap = nullptr;
+	req.flags = flags;
+	req.format = 0;
+	req.nrows = 0;
+	req.unmatched = true;
+	if (kds_dest)
+	{
+		/* (an outer column is NULL whatever its number: there is no outer chunk to hold it against) */
+		if (kds_dest->ncols < 1 || kds_dest->ncols > 1600 ||
+			!projection_mapping_is_sane(tbl, 0x7fffffffu, (int)kds_dest->ncols, src_depth, src_colidx))
+		{
+			*p_errcode = StromError_BadRequestMessage;
+			return nullptr;
+		}
+		req.kds_dest = kds_dest;
+		req.map_depth.assign(src_depth, src_depth + kds_dest->ncols);
+		req.map_colidx.assign(src_colidx, src_colidx + kds_dest->ncols);
+	}
+	if (!tracked_table_quiesce(tbl))
+	{
+		*p_errcode = StromError_HipInternal;
+		return nullptr;
+	}
+	kres->nitems = 0;
+	kres->errcode = StromError_Success;
+	strom_task_impl *task = task_create(tbl->dev, done, arg);
+	gpuhashjoin_launch(task, req);
+	return task;
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+/* RIGHT = inner + (track_matches) + this after the last chunk; FULL = left + the same */
+extern "C" strom_task *
+strom_submit_gpuhashjoin_unmatched(strom_hashjoin_table *tbl, kern_hashjoin *khashjoin,
+								   uint32_t flags, strom_done_cb done, void *arg, int *p_errcode)
+{
+	return submit_unmatched_common(tbl, khashjoin, nullptr, nullptr, nullptr, flags, done, arg, p_errcode);
+}
+
+extern "C" strom_task *
+strom_submit_gpuhashjoin_unmatched_projection(strom_hashjoin_table *tbl, kern_hashjoin *khashjoin,
+											  kern_data_store *kds_dest,
+											  const int32_t *src_depth, const int32_t *src_colidx,
+											  uint32_t flags, strom_done_cb done, void *arg, int *p_errcode)
+{
+	if (!kds_dest || !src_depth || !src_colidx ||
+		(kds_dest->format != KDS_FORMAT_TUPSLOT && kds_dest->format != KDS_FORMAT_ROW_FLAT) ||
+		(kds_dest->format == KDS_FORMAT_ROW_FLAT &&
+		 (size_t)kds_dest->length < KDS_HEAD_LENGTH(kds_dest->ncols) +
+		 STROMALIGN(sizeof(kern_blkitem) * (size_t)kds_dest->maxblocks) +
+		 STROMALIGN(sizeof(kern_rowitem) * (size_t)kds_dest->nrooms)))
+	{
+		if (p_errcode)
+			*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	return submit_unmatched_common(tbl, khashjoin, kds_dest, src_depth, src_colidx, flags, done, arg, p_errcode);
+}
+
+/* the whole flag area through hashjoin_matches_kernel: op 0 clears the "matched" bits, op 1 ORs an image in */
+static int
+tracked_table_matches_op(strom_hashjoin_table *tbl, const void *image, size_t len, int op)
+{
+	if (!tbl || tbl->track_depth == 0 || (op == 1 && (!image || len != tbl->head.track_len)))
+		return StromError_BadRequestMessage;
+	if (!tracked_table_quiesce(tbl))
+		return StromError_HipInternal;
+	Device	   *dev = tbl->dev;
+	int			errcode = 0;
+	if (op == 1)
+	{
+		/* an image of ANOTHER table of the same length would be ORed in silently: everything but the
+		 * "matched" bit -- where entries start, and where in their granule -- must be this table's */
+		std::vector<unsigned char> own(len);
+		const unsigned char *theirs = (const unsigned char *)image;
+		if (hipMemcpy(own.data(), tbl->d_index + tbl->head.track_off, len, hipMemcpyDeviceToHost) != hipSuccess)
+			return StromError_HipInternal;
+		for (size_t i = 0; i < len; i++)
+			if ((own[i] ^ theirs[i]) & ~0x40u)			/* HASHJOIN_FLAG_MATCHED (strom_hashjoin.h) */
+				return StromError_BadRequestMessage;
+	}
+	hipFunction_t fn = tbl->prog->get_function(dev, "hashjoin_matches_kernel", &errcode);
+	if (!fn)
+		return errcode;
+	hipStream_t	stream = dev->streams[0];
+	void	   *d_image = nullptr;
+	if (op == 1)
+	{
+		d_image = dev->pool.alloc(len);
+		if (!d_image)
+			return StromError_OutOfMemory;
+	}
+	void	   *a_ix = tbl->d_index;
+	const void *a_image = d_image;
+	cl_int		a_op = op;
+	void	   *args[] = { &a_ix, &a_image, &a_op };
+	unsigned	nwords = tbl->head.track_len / 4;
+	unsigned	grid = std::max(1u, std::min<unsigned>((nwords + 255) / 256, (unsigned)dev->prop.multiProcessorCount * 8));
+	bool		ok = ((op != 1 || hipMemcpyAsync(d_image, image, len, hipMemcpyHostToDevice, stream) == hipSuccess) &&
+					  hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, stream, args, nullptr) == hipSuccess &&
+					  hipStreamSynchronize(stream) == hipSuccess);
+	if (d_image)
+		dev->pool.release(d_image);
+	return ok ? 0 : StromError_HipInternal;
+}
+
+/* a rescan: every entry is unmatched again */
+extern "C" int
+strom_hashjoin_table_reset_matches(strom_hashjoin_table *tbl)
+{
+	STROM_ABI_TRY
+	return tracked_table_matches_op(tbl, nullptr, 0, 0);
+	STROM_ABI_CATCH(StromError_HipInternal, (int *)nullptr)
+}
+
+/* the multi-GPU seam: every rank holds the same table and sees a shard of the outer rows; an entry is
+ * unmatched only if it is unmatched on all ranks.  _fetch copies the flag area out (_matches_length
+ * bytes; 0 for a table without tracking), _merge ORs such an image of the same length in. */
+extern "C" size_t
+strom_hashjoin_table_matches_length(strom_hashjoin_table *tbl)
+{
+	return (tbl && tbl->track_depth != 0 ? (size_t)tbl->head.track_len : 0);
+}
+
+extern "C" int
+strom_hashjoin_table_matches_fetch(strom_hashjoin_table *tbl, void *buf, size_t len)
+{
+	STROM_ABI_TRY
+	if (!tbl || tbl->track_depth == 0 || !buf || len < tbl->head.track_len)
+		return StromError_BadRequestMessage;
+	if (!tracked_table_quiesce(tbl) ||
+		hipMemcpy(buf, tbl->d_index + tbl->head.track_off, tbl->head.track_len, hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_HipInternal;
+	return 0;
+	STROM_ABI_CATCH(StromError_HipInternal, (int *)nullptr)
+}
+
+extern "C" int
+strom_hashjoin_table_matches_merge(strom_hashjoin_table *tbl, const void *buf, size_t len)
+{
+	STROM_ABI_TRY
+	return tracked_table_matches_op(tbl, buf, len, 1);
+	STROM_ABI_CATCH(StromError_HipInternal, (int *)nullptr)
+}
 
 /*
  * inner column 'col' (0-based, attlen bytes wide) of a single-relation table
@@ -1522,20 +1745,22 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		p_errcode = &dummy;
 	*p_errcode = 0;
 	strom_task_impl *task = static_cast<strom_task_impl *>(handle);
-	if (!task || !tbl || !outer || ncols < 1 || ncols > 64 || !src_depth || !src_colidx || !type_oids)
+	if (!task || !tbl || ncols < 1 || ncols > 64 || !src_depth || !src_colidx || !type_oids)
 	{
 		*p_errcode = StromError_BadRequestMessage;
 		return nullptr;
 	}
 	task_wait_completed(task);
+	/* the records of the unmatched pass have no outer row: outer == NULL goes with them and with no
+	 * other task; every column of depth 0 is then NULL, whatever its number */
 	if (!task->res_is_join || !task->keep_main || task->errcode != 0 || !task->main_devptr ||
-		outer->dindex != tbl->dev->dindex)
+		(outer == nullptr) != task->res_is_unmatched || (outer && outer->dindex != tbl->dev->dindex))
 	{
 		/* not a finished GpuHashJoin with STROM_RESULTS_ON_DEVICE */
 		*p_errcode = (task->errcode ? task->errcode : StromError_BadRequestMessage);
 		return nullptr;
 	}
-	if (!projection_mapping_is_sane(tbl, outer->head.ncols, ncols, src_depth, src_colidx))
+	if (!projection_mapping_is_sane(tbl, outer ? outer->head.ncols : 0x7fffffffu, ncols, src_depth, src_colidx))
 	{
 		/* the kernel indexes colmeta[] / the column directory with these */
 		*p_errcode = StromError_BadRequestMessage;
@@ -1566,7 +1791,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		if (!is_text_type(type_oids[i]))
 			continue;
 		any_text = true;
-		if (src_depth[i] == 0 && outer->head.format == KDS_FORMAT_TUPSLOT)
+		if (src_depth[i] == 0 && outer && outer->head.format == KDS_FORMAT_TUPSLOT)
 		{
 			*p_errcode = StromError_BadRequestMessage;		/* a TUPSLOT chunk holds no datum bytes */
 			return nullptr;
@@ -1638,7 +1863,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 	 * slot-indexed arrays (hashjoin_build_dimcol_kernel) instead of the entries
 	 */
 	std::vector<cl_ulong> dimptr(2 * (size_t)ncols, 0);
-	bool	use_dim = (tbl->ntables == 1 && tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT && tbl->head.rel[0].unique &&
+	bool	use_dim = (outer && tbl->ntables == 1 && tbl->head.rel[0].mode == HASHJOIN_MODE_DIRECT && tbl->head.rel[0].unique &&
 					   outer->head.format == KDS_FORMAT_COLUMN &&
 					   strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_ELIGIBLE 1") != nullptr &&
 					   !getenv("STROM_HASHJOIN_NO_DIMCOLS"));
@@ -1697,7 +1922,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 		}
 		void	   *a_khj = task->main_devptr;
 		const void *a_km = tbl->d_kmhash;
-		const void *a_kds = outer->devptr;
+		const void *a_kds = (outer ? outer->devptr : nullptr);
 		const void *a_toast = nullptr;
 		if (any_text)
 		{
@@ -1811,7 +2036,7 @@ strom_hashjoin_project_column(strom_task *handle, strom_hashjoin_table *tbl, str
 			break;
 		}
 		cl_int	failed = 0;
-		result = new strom_dstore{d_dst, off, outer->dindex, true, {}};
+		result = new strom_dstore{d_dst, off, tbl->dev->dindex, true, {}};
 		if (hipMemcpyAsync(&result->head, d_dst, offsetof(kern_data_store, colmeta),
 						   hipMemcpyDeviceToHost, stream) != hipSuccess ||
 			hipMemcpyAsync(&failed, d_aux + 4 * (size_t)ncols, sizeof(cl_int),

@@ -2519,6 +2519,10 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 	 * index and unique keys, joined on a plain outer column; a resident COLUMN chunk; all on the session's device */
 	int			outer_ncols = (int)outer->head.ncols;
 	bool		ok = (!jtask || (jtask->res_is_join && jtask->keep_main && jtask->errcode == 0 && jtask->main_devptr));
+	/* the records of the unmatched pass of a RIGHT / FULL join have no outer row (word 0 == 0): the
+	 * joined fold reads the outer chunk at word 0 - 1 and would leave it.  They go through
+	 * strom_hashjoin_project_column(task, tbl, NULL, ..) and a plain fold. */
+	ok = ok && !(jtask && jtask->res_is_unmatched);
 	ok = ok && outer->head.format == KDS_FORMAT_COLUMN && outer->dindex == sess->dev->dindex;
 	m->ncols = ncols;
 	m->nrels = ntbls;
@@ -2530,6 +2534,10 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 			  /* a lookup runs the aggregate program only: a WHERE that lives in the join
 			   * program would silently not be applied */
 			  !(entry != PREAGG_JOINED && has_outer_qual) &&
+			  /* ... and probes without running the join program: a table whose program tracks
+			   * matches (RIGHT / FULL) would keep every flag clear and its unmatched pass would
+			   * silently emit matched entries.  The joined fold is fine: the join ran and flagged. */
+			  !(entry != PREAGG_JOINED && strom_hashjoin_table_tracked_depth(tbls[r]) != 0) &&
 			  key_attno >= 1 && key_attno <= outer_ncols && tbl_dindex == sess->dev->dindex);
 		m->key_col[r] = key_attno - 1;
 	}
@@ -2658,7 +2666,8 @@ build_snowflake_mapping(strom_gpupreagg *sess, strom_hashjoin_table *const *tbls
 		cl_long		key_min;
 		cl_uint		nslots;
 		if (hashjoin_table_direct_info(tbls[d - 1], &key_min, &nslots, &key_attno, &tbl_dindex, &has_outer_qual) != 0 ||
-			has_outer_qual || key_attno < 1 || tbl_dindex != sess->dev->dindex)
+			has_outer_qual || key_attno < 1 || tbl_dindex != sess->dev->dindex ||
+			strom_hashjoin_table_tracked_depth(tbls[d - 1]) != 0)		/* (as build_fold_mapping says) */
 			return StromError_BadRequestMessage;
 		if (parent[d - 1] == 0)
 		{

@@ -192,14 +192,42 @@ class GpuHashJoin(object):
             res.retried = True
         return res
 
+    def _default_rooms(self, chunk):
+        """result room of a projection: the chunk's rows x ratio x 1.1 (gpuhashjoin.c:2513-2514); for
+        the unmatched pass (chunk is None) every entry of the tracked relation"""
+        if chunk is None:
+            return self.table_info(self.tracked_depth())["nentries"] + 1
+        nrows = chunk.nitems if isinstance(chunk, runtime.DeviceStore) else KdsHead(chunk).nitems
+        return int(nrows * self.ratio * 1.1) + 1
+
+    def _submit_projection(self, chunk, khj, dest, depth, colidx):
+        """join + TUPSLOT / ROW_FLAT projection of one chunk; chunk None: of the unmatched pass"""
+        err = ctypes.c_int(0)
+        if chunk is None:
+            task = lib.strom_submit_gpuhashjoin_unmatched_projection(
+                self.table, khj.ctypes.data, dest.ctypes.data,
+                depth.ctypes.data, colidx.ctypes.data, 0, None, None, ctypes.byref(err))
+            if not task:
+                raise runtime.StromError(err.value, "strom_submit_gpuhashjoin_unmatched_projection")
+            return task
+        if isinstance(chunk, runtime.DeviceStore):
+            kds_host, kds_dev = None, chunk.handle
+        else:
+            kds_host, kds_dev = chunk.ctypes.data, None
+        task = lib.strom_submit_gpuhashjoin_projection(
+            self.table, khj.ctypes.data, kds_host, kds_dev, None, dest.ctypes.data,
+            depth.ctypes.data, colidx.ctypes.data, 0, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpuhashjoin_projection")
+        return task
+
     def join_chunk_project(self, chunk, dest_columns, nrooms=None):
         """join + kern_gpuhashjoin_projection_slot: dest_columns is a list of
         (depth, attno, sqltype) -- depth 0 is the outer chunk, d the d-th inner
         relation.  Returns (nitems, [(values, isnull)] per destination column)"""
         from .kds import SQL_TYPES, KDS_HEAD_FIXED
-        nrows = chunk.nitems if isinstance(chunk, runtime.DeviceStore) else KdsHead(chunk).nitems
         if nrooms is None:
-            nrooms = int(nrows * self.ratio * 1.1) + 1
+            nrooms = self._default_rooms(chunk)
         ncols = len(dest_columns)
         for attempt in range(2):
             head_len = (KDS_HEAD_FIXED + 8 * ncols + 15) & ~15
@@ -222,16 +250,7 @@ class GpuHashJoin(object):
             depth = np.array([d for d, _, _ in dest_columns], dtype=np.int32)
             colidx = np.array([a - 1 for _, a, _ in dest_columns], dtype=np.int32)
             khj, res_off = self._make_khj(nrooms, True)
-            if isinstance(chunk, runtime.DeviceStore):
-                kds_host, kds_dev = None, chunk.handle
-            else:
-                kds_host, kds_dev = chunk.ctypes.data, None
-            err = ctypes.c_int(0)
-            task = lib.strom_submit_gpuhashjoin_projection(
-                self.table, khj.ctypes.data, kds_host, kds_dev, None, dest.ctypes.data,
-                depth.ctypes.data, colidx.ctypes.data, 0, None, None, ctypes.byref(err))
-            if not task:
-                raise runtime.StromError(err.value, "strom_submit_gpuhashjoin_projection")
+            task = self._submit_projection(chunk, khj, dest, depth, colidx)
             rc = lib.strom_task_wait(task, None)
             nitems = int(np.frombuffer(khj[res_off + 8:res_off + 12].tobytes(), dtype=np.uint32)[0])
             if rc == ERR_NOSPACE and attempt == 0:
@@ -258,9 +277,8 @@ class GpuHashJoin(object):
         result records); DataStoreNoSpace is answered by a larger store, like
         gpuhashjoin.c:4330-4425."""
         from .kds import SQL_TYPES, KDS_HEAD_FIXED
-        nrows = chunk.nitems if isinstance(chunk, runtime.DeviceStore) else KdsHead(chunk).nitems
         if nrooms is None:
-            nrooms = int(nrows * self.ratio * 1.1) + 1
+            nrooms = self._default_rooms(chunk)
         ncols = len(dest_columns)
         if data_bytes is None:
             data_bytes = 64 * nrooms
@@ -287,16 +305,7 @@ class GpuHashJoin(object):
             depth = np.array([d for d, _, _ in dest_columns], dtype=np.int32)
             colidx = np.array([a - 1 for _, a, _ in dest_columns], dtype=np.int32)
             khj, res_off = self._make_khj(nrooms, True)
-            if isinstance(chunk, runtime.DeviceStore):
-                kds_host, kds_dev = None, chunk.handle
-            else:
-                kds_host, kds_dev = chunk.ctypes.data, None
-            err = ctypes.c_int(0)
-            task = lib.strom_submit_gpuhashjoin_projection(
-                self.table, khj.ctypes.data, kds_host, kds_dev, None, dest.ctypes.data,
-                depth.ctypes.data, colidx.ctypes.data, 0, None, None, ctypes.byref(err))
-            if not task:
-                raise runtime.StromError(err.value, "strom_submit_gpuhashjoin_projection")
+            task = self._submit_projection(chunk, khj, dest, depth, colidx)
             rc = lib.strom_task_wait(task, None)
             nitems = int(np.frombuffer(khj[res_off + 8:res_off + 12].tobytes(), dtype=np.uint32)[0])
             if rc == ERR_NOSPACE and attempt < 7:
@@ -328,9 +337,13 @@ class GpuHashJoin(object):
         if not zone_maps:
             oids = -oids                                     # widths only: no min/max pass
         for attempt in range(2):
-            pending = self.submit(chunk, nrooms=nrooms, row_map=row_map, flags=STROM_RESULTS_ON_DEVICE)
+            if chunk is None:
+                pending = self.submit_unmatched(nrooms=nrooms, flags=STROM_RESULTS_ON_DEVICE)
+            else:
+                pending = self.submit(chunk, nrooms=nrooms, row_map=row_map, flags=STROM_RESULTS_ON_DEVICE)
             err = ctypes.c_int(0)
-            handle = lib.strom_hashjoin_project_column(pending[0], self.table, chunk.handle, ncols,
+            handle = lib.strom_hashjoin_project_column(pending[0], self.table,
+                                                       None if chunk is None else chunk.handle, ncols,
                                                        depth.ctypes.data, colidx.ctypes.data,
                                                        oids.ctypes.data, ctypes.byref(err))
             res = self.collect(pending)
@@ -340,6 +353,67 @@ class GpuHashJoin(object):
             if not handle:
                 raise runtime.StromError(err.value, "strom_hashjoin_project_column")
             return runtime.DeviceStore(handle, res.nitems), res.nitems
+
+    # ---- RIGHT / FULL joins: a program with (track_matches) on its last relation ----------------
+    def tracked_depth(self):
+        """the relation whose entries the probes flag (1-based), 0: the program does not track"""
+        return lib.strom_hashjoin_table_tracked_depth(self.table)
+
+    def submit_unmatched(self, nrooms=None, flags=0):
+        if nrooms is None:
+            nrooms = self._default_rooms(None)
+        khj, res_off = self._make_khj(nrooms, not (flags & STROM_RESULTS_ON_DEVICE))
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpuhashjoin_unmatched(self.table, khj.ctypes.data, flags, None, None,
+                                                      ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpuhashjoin_unmatched")
+        return (task, khj, res_off, None, None, flags)
+
+    def unmatched(self, nrooms=None, flags=0):
+        """after the last chunk: one record (0, .., 0, entry offset) per entry of the tracked relation
+        that no chunk matched -- word 0 == 0 is "no outer row".  Comes after every join of this table
+        submitted before it; resize-and-retry on DataStoreNoSpace as join_chunk."""
+        res = self.collect(self.submit_unmatched(nrooms=nrooms, flags=flags))
+        if res.errcode == ERR_NOSPACE:
+            res = self.collect(self.submit_unmatched(nrooms=res.nitems, flags=flags))
+            res.retried = True
+        return res
+
+    def unmatched_project(self, dest_columns, nrooms=None):
+        """join_chunk_project of the unmatched pass: every column of depth 0 is NULL"""
+        return self.join_chunk_project(None, dest_columns, nrooms=nrooms)
+
+    def unmatched_project_rows(self, dest_columns, nrooms=None, data_bytes=None):
+        """join_chunk_project_rows of the unmatched pass"""
+        return self.join_chunk_project_rows(None, dest_columns, nrooms=nrooms, data_bytes=data_bytes)
+
+    def unmatched_to_column(self, dest_columns, nrooms=None, zone_maps=True):
+        """join_to_column of the unmatched pass: (DeviceStore, nitems)"""
+        return self.join_to_column(None, dest_columns, nrooms=nrooms, zone_maps=zone_maps)
+
+    def reset_matches(self):
+        """a rescan: every entry of the tracked relation is unmatched again"""
+        rc = lib.strom_hashjoin_table_reset_matches(self.table)
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_hashjoin_table_reset_matches")
+
+    def matches_image(self):
+        """the flag area (uint8 per 32-byte granule of the table: 0x80 an entry starts there, 0x40 it was matched),
+        for merge_matches() of another rank's table over the same kern_multihash"""
+        n = lib.strom_hashjoin_table_matches_length(self.table)
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = lib.strom_hashjoin_table_matches_fetch(self.table, out.ctypes.data, n)
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_hashjoin_table_matches_fetch")
+        return out[:n]
+
+    def merge_matches(self, image):
+        """OR another rank's matches_image() in: an entry is unmatched only if it is on every rank"""
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rc = lib.strom_hashjoin_table_matches_merge(self.table, image.ctypes.data, len(image))
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_hashjoin_table_matches_merge")
 
     def end(self):
         if self.table:

@@ -584,7 +584,9 @@ int			strom_hashjoin_table_matches_merge(strom_hashjoin_table *tbl, const void *
  * plain outer column: inner columns then come from slot-indexed arrays the
  * table builds on first use.  Anything else -- a table whose program has a
  * (jointype left | semi | anti) relation included -- answers BadRequest with
- * nothing launched and the caller goes through strom_hashjoin_project_column().
+ * nothing launched and the caller goes through strom_hashjoin_project_column()
+ * (the pairs of a LEFT join are not folded here; a LEFT / SEMI / ANTI join over
+ * unique keys needs no pairs at all: strom_submit_gpupreagg_lookup_typed).
  * Text / character(n): a variable of the program with one of these types
  * must be a column of 'outer' -- src_depth 0, type_oids STROM_TEXTOID /
  * STROM_BPCHARNOID as the variable's own type, onto a column with attlen
@@ -609,8 +611,10 @@ strom_task *strom_submit_gpupreagg_joined(strom_gpupreagg *sess, strom_task *joi
  * outer columns is the aggregate program's (qual ...).  Same requirements on
  * the table (one relation, DIRECT index, unique keys, key = a plain outer
  * column of int4 / int8 / date width, an INNER join: a table whose program
- * names another join type is refused, here and by _lookup_star / _lookup_snowflake,
- * with nothing launched); anything else answers BadRequest.
+ * names another join type is refused, here and by _lookup_star / _lookup_snowflake
+ * / _lookup_typed, with nothing launched -- LEFT / SEMI / ANTI are asked of the FOLD,
+ * over the same inner table: strom_submit_gpupreagg_lookup_typed); anything else
+ * answers BadRequest.
  * The JOIN program's own qual and parameters are NOT evaluated on this path
  * (only the aggregate program runs): a table whose program carries a
  * pulled-up outer qual or a join qual is refused with BadRequest -- put the
@@ -635,7 +639,8 @@ strom_task *strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
  * join over all relations: a row is folded only if EVERY relation has a partner for it (key not
  * NULL, inside the table's key range, slot present); the WHERE is the aggregate program's (qual
  * ...), evaluated before any probe when it reads outer columns only, and an error in it is raised
- * only for a row that has a partner in every relation.
+ * only for a row that has a partner in every relation.  (Relations that join LEFT, SEMI or ANTI:
+ * strom_submit_gpupreagg_lookup_typed, the same tables with a join type each.)
  * Two fact columns that point at the SAME dimension are two tables: a table's program names one
  * outer column, so the dimension is built once per fact column that joins it.
  * ntbls == 1 is strom_submit_gpupreagg_lookup.  BadRequest, and nothing is launched: ntbls
@@ -667,6 +672,58 @@ int			strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, cons
 												char *buf, size_t buflen);
 
 /*
+ * ... and the same single pass for LEFT, SEMI and ANTI relations: "fact LEFT JOIN dim GROUP BY
+ * dim.g", "WHERE EXISTS (SELECT 1 FROM dim WHERE dim.k = fact.k)", "WHERE NOT EXISTS (...)".
+ * jointypes[d - 1] says how relation d joins the fact rows, in the values of the join program's
+ * (jointype ...): 0 inner, 1 left, 2 semi, 3 anti.  It is an argument of the FOLD: a lookup never
+ * runs the join program, the table only lends its index and its slot records -- so tbls[] are
+ * exactly what strom_submit_gpupreagg_lookup_star takes (one-relation INNER programs, DIRECT index,
+ * unique keys, no qual, not tracked, on the session's device; a table built from a (jointype ...)
+ * program stays refused).
+ * A row has a partner in relation d when its key is not NULL, inside the table's key range, and
+ * the slot is present.  A row is folded iff every inner and every semi relation has a partner for
+ * it and no anti relation has one; a left relation never drops a row.  The columns a left
+ * relation serves are NULL for a row without a partner; semi and anti relations serve no column.
+ * All relations are joined on fact columns, so they commute.  The aggregate program's (qual ...) is
+ * the WHERE, applied after the join: over a left relation's column it sees NULL for partner-less
+ * rows; over fact columns alone it still runs before any probe and drops a row under every join
+ * type.  An error (in the qual, in the row, an unreadable text datum) is raised only for a row
+ * that is folded.  Duplicate inner keys are not unique keys: such a SEMI / ANTI join goes through
+ * the one-pass join, its row map and strom_submit_gpupreagg with that map.
+ * jointypes all zero IS strom_submit_gpupreagg_lookup_star: its code path, error codes and
+ * programs.  ntbls == 1 is the one-table kernel with every record form it reads, always built for
+ * the mapping (GPUPREAGG_LOOKUP_JOINTYPE; STROM_GPUPREAGG_LOOKUP_GENERIC does not apply); 2 ..
+ * STROM_LOOKUP_STAR_MAXRELS relations are the star kernels (GPUPREAGG_STAR_JOINTYPE_<d>).
+ * BadRequest, and nothing is launched: jointypes NULL or a value outside 0 .. 3, a virtual column
+ * mapped to a semi or anti relation, and everything strom_submit_gpupreagg_lookup_star refuses.
+ */
+strom_task *strom_submit_gpupreagg_lookup_typed(strom_gpupreagg *sess,
+												strom_hashjoin_table *const *tbls, int ntbls,
+												const int32_t *jointypes,	/* [ntbls] 0 inner, 1 left, 2 semi, 3 anti */
+												strom_dstore *outer,
+												int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+												const int32_t *type_oids,
+												strom_done_cb done, void *arg, int *p_errcode);
+/*
+ * The define block of such a mapping, as strom_gpupreagg_lookup_star_defines gives the star's (no
+ * device needed).  ntbls == 1: the one-table kernels' block (any record length they read), else
+ * the star's; an inner relation adds no line, so an all-inner star gives
+ * strom_gpupreagg_lookup_star_defines' text byte for byte.  -1: the text does not fit, no valid
+ * mapping, a join type outside 0 .. 3, or a column under a semi / anti relation.
+ */
+int			strom_gpupreagg_lookup_typed_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+												 const int32_t *narrow, const uint64_t *inner_mask,
+												 const int32_t *jointypes, char *buf, size_t buflen);
+
+/*
+ * The define blocks of the programs this session has built FOR a mapping so far (one-table, star, typed; a
+ * checked retry's begins with GPUPREAGG_CHECKED), each followed by an empty line: what a request's tables came
+ * to -- record length and form, served columns, join types -- for a planner's log or a test.  Returns the
+ * length of the text (buf NULL: only that), or -1 if it does not fit buflen.
+ */
+int			strom_gpupreagg_mapping_defines(strom_gpupreagg *sess, char *buf, size_t buflen);
+
+/*
  * ... and a SNOWFLAKE: a relation keyed by ANOTHER RELATION's column ("lineitem -> orders ->
  * customer", "fact -> product -> brand").  The fold kernels never decide a probe from another
  * relation's record; they do not have to: the tables are DIRECT with unique keys, so a child
@@ -682,7 +739,8 @@ int			strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, cons
  * date or int8; ignored for a root).  src_depth[i] is 0 .. ntbls as in the star: any relation may
  * serve columns, one that serves none is an existence filter.  An inner join: a row is folded
  * only if every relation of the tree has a partner (a NULL link, a link outside the child's key
- * range or in one of its holes: no partner).
+ * range or in one of its holes: no partner); a non-inner link is not offered -- the relations of
+ * strom_submit_gpupreagg_lookup_typed are all joined on fact columns.
  * parent[] all zero is strom_submit_gpupreagg_lookup_star, ntbls == 1 strom_submit_gpupreagg_lookup:
  * their code paths, their error codes.  BadRequest, and nothing is launched: a NULL argument, ntbls
  * outside 1 .. STROM_LOOKUP_SNOWFLAKE_MAXRELS, parent[d - 1] outside 0 .. d - 1, more than

@@ -145,6 +145,11 @@ PROTOTYPES = {
                                                       c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
     "strom_gpupreagg_lookup_star_defines": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                        ctypes.c_char_p, c_size_t]),
+    "strom_submit_gpupreagg_lookup_typed": (c_void_p, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "strom_gpupreagg_lookup_typed_defines": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                        ctypes.c_char_p, c_size_t]),
+    "strom_gpupreagg_mapping_defines": (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
     "strom_submit_gpupreagg_lookup_snowflake": (c_void_p, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                            ctypes.POINTER(c_int)]),

@@ -1560,7 +1560,10 @@ gpupreagg_dense_joined(kern_gpupreagg *kgpreagg,
  * DIRECT index and unique keys: the outer COLUMN chunk streams through the
  * tile loader exactly as in gpupreagg_dense_column, a row's slot is
  * outer key - key_min, a row without a partner (NULL key, key outside the
- * table, empty slot) is dropped, and a virtual column of depth 1 comes from
+ * table, empty slot) is dropped -- under an inner or semi join; an anti join
+ * folds exactly those rows, a left join every row, the dimension's columns
+ * NULL without a partner (GPUPREAGG_LOOKUP_JOINTYPE, in the program built for
+ * the mapping) -- and a virtual column of depth 1 comes from
  * the table's slot-indexed arrays (a few MB, L2-resident).  No result pairs
  * are written or read at all.  The program's (var N ...) and its qual see
  * the same virtual relation as gpupreagg_dense_joined; int4 / int8 keys.
@@ -1660,6 +1663,30 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 #else
 #define LOOKUP_GLOBAL(T, p)		(*(const __attribute__((address_space(1))) T *)(p))
 #endif
+	/*
+	 * The join type (GPUPREAGG_LOOKUP_JOINTYPE: 0 inner, 1 left, 2 semi, 3 anti -- the values of
+	 * HASHJOIN_JOIN_TYPE_<d>; absent: inner) is a fact of the request like the mapping, and decides two
+	 * things only: how the relation's presence enters "is this row folded", and whether its columns
+	 * are forced to NULL.  inner and semi fold a row that has a partner, anti one that has none, left
+	 * every row -- with the relation's columns NULL where there is no partner.  So left and anti
+	 * need what inner never did: "no partner" apart from "not folded", because a row whose key is
+	 * NULL or outside the table is not probed -- it reads slot 0, which is always an occupied record
+	 * (key_min is a key that exists) -- and must count as absent whatever that holds.  Both masks
+	 * share the tile's gone[] words (bit j: not folded, bit 4 + j: no key for a probe): the kernel
+	 * has no registers to spare (profiles/lookup_join_types_resources.txt).
+	 */
+#if defined(GPUPREAGG_LOOKUP_JOINTYPE)
+#if !defined(GPUPREAGG_LOOKUP_INNER_MASK) || GPUPREAGG_LOOKUP_JOINTYPE < 0 || GPUPREAGG_LOOKUP_JOINTYPE > 3
+#error "GPUPREAGG_LOOKUP_JOINTYPE: 0 .. 3, in a program built for its mapping"
+#endif
+#if (GPUPREAGG_LOOKUP_JOINTYPE == 2 || GPUPREAGG_LOOKUP_JOINTYPE == 3) && GPUPREAGG_LOOKUP_INNER_MASK != 0
+#error "a semi or anti relation serves no column"
+#endif
+	constexpr int	jointype = GPUPREAGG_LOOKUP_JOINTYPE;
+#else
+	constexpr int	jointype = 0;
+#endif
+	constexpr bool	keeps_absent = (jointype == 1 || jointype == 3);	/* left, anti: a partner-less row may be folded */
 #define X(attno,colidx,NAME)													\
 	const bool	inner_##attno = LOOKUP_INNER(colidx);								\
 	const cl_uint recoff_##attno = strom_uniform((cl_uint)jmap->c[colidx].dimvalues);	\
@@ -1785,7 +1812,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 		 * without a partner look at slot 0, harmlessly.
 		 */
 		cl_uint		slot[GPUPREAGG_QUADS][4];
-		cl_uint		gone[GPUPREAGG_QUADS];			/* bit j: no partner */
+		cl_uint		gone[GPUPREAGG_QUADS];			/* bit j: not folded (inner, semi: no partner); left and
+													 * anti, bit 4 + j: not probed, so no partner */
 		cl_uint		qual_ok[GPUPREAGG_QUADS];		/* bit j: the qual was seen to pass, without an error */
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
@@ -1797,7 +1825,9 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 			for (int j = 0; j < 4; j++)
 			{
 				cl_ulong	s64 = (cl_ulong)((cl_long)keyq[k][j] - key_min);
-				bool		live = ((full_tile || row0 + j < nitems) && ((keynn[k] >> j) & 1) && s64 < nslots);
+				bool		haskey = (((keynn[k] >> j) & 1) && s64 < nslots);
+				/* (left, anti: a key without a slot does not drop the row -- it is absent, unprobed) */
+				bool		live = ((full_tile || row0 + j < nitems) && (keeps_absent || haskey));
 				if (qual_first && live)
 				{
 					strom_kvars	KV;
@@ -1815,8 +1845,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 					live = !(qerr == StromError_Success && !EVAL(rc));
 					qual_ok[k] |= ((qerr == StromError_Success && EVAL(rc)) ? (1u << j) : 0u);
 				}
-				slot[k][j] = (live ? (cl_uint)s64 : 0u);
-				gone[k] |= (live ? 0u : (1u << j));
+				slot[k][j] = ((live && haskey) ? (cl_uint)s64 : 0u);
+				gone[k] |= (live ? 0u : (1u << j)) | ((keeps_absent && !haskey) ? (16u << j) : 0u);
 			}
 		}
 		cl_uint	words[GPUPREAGG_QUADS][4][4];	/* records of 8 / 16 bytes: the whole record, fetched in ONE load */
@@ -1877,7 +1907,9 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 				flags[j] = words[k][j][0];
 				ab |= ((flags[j] & 1u) ? 0u : (1u << j));
 			}
-			gone[k] |= ab;
+			/* the record's presence bit joins the key's verdict; then the join type's select */
+			const cl_uint absent = (keeps_absent ? ((gone[k] >> 4) | ab) : ab);
+			gone[k] |= (jointype == 1 ? 0u : jointype == 3 ? (~absent & 0xfu) : ab);
 #define X(attno,colidx,NAME)													\
 			if (inner_##attno)													\
 			{																	\
@@ -1904,7 +1936,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 					T.v_##attno[k][j] = val;									\
 					nn |= (((flags[j] >> recbit_##attno) & 1u) ? 0u : (1u << j));	\
 				}																\
-				T.nn_##attno[k] = nn;											\
+				/* (left: the columns of a row without a partner are NULL, whatever slot 0 says) */	\
+				T.nn_##attno[k] = (jointype == 1 ? (nn & ~absent) : nn);			\
 			}
 			STROM_KVAR_LIST(X)
 #undef X
@@ -2019,8 +2052,10 @@ gpupreagg_packed_lookup(kern_gpupreagg *kgpreagg,
  *
  * "fact JOIN dim1 JOIN dim2 ... GROUP BY": relations 1 .. GPUPREAGG_STAR_NRELS, each a table as
  * gpupreagg_dense_lookup takes ONE of (DIRECT index, unique keys, packed slot records), each
- * probed by an outer column of its own.  An inner join: a row is folded only if every relation
- * has a partner; a virtual column of depth d comes from relation d's slot record.
+ * probed by an outer column of its own.  A row is folded if every inner and semi relation has a
+ * partner for it and no anti relation has one (GPUPREAGG_STAR_JOINTYPE_<d>, absent: inner; the
+ * relations commute); a virtual column of depth d comes from relation d's slot record, and is NULL
+ * where a left relation has no partner.
  *
  * These kernels exist only in a program built FOR the mapping (gpupreagg.cpp:
  * star_mapping_program): the relation count and per relation GPUPREAGG_STAR_RECLEN_<d> /
@@ -2055,6 +2090,20 @@ gpupreagg_packed_lookup(kern_gpupreagg *kgpreagg,
 #define GPUPREAGG_STAR_REL_LIST(M)	M(1) M(2) M(3) M(4)
 #endif
 
+/* relation r's join type (the values of HASHJOIN_JOIN_TYPE_<d>: 0 inner, 1 left, 2 semi, 3 anti); absent: inner */
+#ifndef GPUPREAGG_STAR_JOINTYPE_1
+#define GPUPREAGG_STAR_JOINTYPE_1	0
+#endif
+#ifndef GPUPREAGG_STAR_JOINTYPE_2
+#define GPUPREAGG_STAR_JOINTYPE_2	0
+#endif
+#ifndef GPUPREAGG_STAR_JOINTYPE_3
+#define GPUPREAGG_STAR_JOINTYPE_3	0
+#endif
+#ifndef GPUPREAGG_STAR_JOINTYPE_4
+#define GPUPREAGG_STAR_JOINTYPE_4	0
+#endif
+
 template <int KEYLEN> struct gpupreagg_star_key { typedef cl_int type; };
 template <> struct gpupreagg_star_key<8> { typedef cl_long type; };
 
@@ -2067,6 +2116,13 @@ template <> struct gpupreagg_star_rel<r> {												\
 	static constexpr bool		narrow = (GPUPREAGG_STAR_NARROW_##r != 0);				\
 	static constexpr cl_ulong	inner_mask = GPUPREAGG_STAR_INNER_MASK_##r;				\
 	static constexpr int		nwords = (narrow ? 1 : reclen == 16 ? 4 : 2);			\
+	static constexpr int		jointype = GPUPREAGG_STAR_JOINTYPE_##r;					\
+	/* left, anti: a row without a partner may be folded -- "no partner" is kept apart from "not	\
+	 * folded": bit absent_shift + j of the tile's gone[] words says that row j was not probed here */	\
+	static constexpr bool		keeps_absent = (jointype == 1 || jointype == 3);		\
+	static constexpr int		absent_shift = 4 * r;									\
+	static_assert(jointype >= 0 && jointype <= 3, "star join type");						\
+	static_assert(jointype < 2 || inner_mask == 0, "a semi or anti relation serves no column");	\
 	static_assert(GPUPREAGG_STAR_KEYLEN_##r == 4 || GPUPREAGG_STAR_KEYLEN_##r == 8, "star key width");	\
 	static_assert(narrow ? (reclen == 2 || reclen == 4) : (reclen == 8 || reclen == 16),	\
 				  "star slot record: 2 / 4 bytes narrow, 8 or 16 bytes");					\
@@ -2180,7 +2236,7 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 #undef M
 	/* a qual that reads outer columns only is evaluated BEFORE any probe (see
 	 * gpupreagg_dense_lookup_body); gpupreagg_dense_row evaluates it again, errors included, for
-	 * the rows that have a partner in every relation */
+	 * the rows that are folded (all inner: that have a partner in every relation) */
 	const bool	qual_first = ((GPUPREAGG_QUAL_VARMASK & GPUPREAGG_STAR_INNER_ALL) == 0 && GPUPREAGG_QUAL_VARMASK != 0);
 	/* (an inner column may be NULL whatever the chunk's bitmaps say) */
 	const cl_uint rowflags = ((any_nulls || GPUPREAGG_STAR_INNER_ALL != 0) ? 0u : ROWFLAG_ALL_NOTNULL);
@@ -2211,17 +2267,32 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 		P.w[k][j][0] = (cl_uint)s64;
 		return ((P.keynn[k] >> j) & 1) && s64 < P.nslots;
 	};
-	/* the probes of relation P: one load per row, dead rows at slot 0 */
+	/* relation P's verdict on the key of row (k, j): an inner or semi relation drops the row, a left
+	 * or anti one only notes that it has no partner there (and will not be probed) */
+	auto key_verdict = [&](auto &P, int k, int j, bool live, cl_uint &gone_k) -> bool
+	{
+		typedef typename gpupreagg_star_unref<decltype(P)>::type::rel rel;
+		bool		haskey = key_to_slot(P, k, j);
+		if (rel::keeps_absent)
+		{
+			gone_k |= (haskey ? 0u : (1u << (rel::absent_shift + j)));
+			return live;
+		}
+		return haskey && live;
+	};
+	/* the probes of relation P: one load per row; dead rows, and those a left or anti relation
+	 * has no slot for, at slot 0 */
 	auto probe = [&](auto &P, const cl_uint (&gone)[GPUPREAGG_QUADS])
 	{
 		typedef typename gpupreagg_star_unref<decltype(P)>::type::rel rel;
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
+			cl_uint		masked = (rel::keeps_absent ? (gone[k] | (gone[k] >> rel::absent_shift)) : gone[k]);
 #pragma unroll
 			for (int j = 0; j < 4; j++)
 			{
-				cl_uint		slot = (((gone[k] >> j) & 1) ? 0u : P.w[k][j][0]);
+				cl_uint		slot = (((masked >> j) & 1) ? 0u : P.w[k][j][0]);
 				const char *rec = P.recs + (size_t)rel::reclen * slot;
 				if (rel::narrow)
 					P.w[k][j][0] = (rel::reclen == 2 ? (cl_uint)STAR_GLOBAL(cl_ushort, rec) : STAR_GLOBAL(cl_uint, rec));
@@ -2250,7 +2321,8 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 		cl_uint		tile_base = tile * GPUPREAGG_TILE_ROWS;
 		bool		full_tile = (tile_base + GPUPREAGG_TILE_ROWS <= nitems);
 		gpupreagg_column_tile T;
-		cl_uint		gone[GPUPREAGG_QUADS];			/* bit j: no partner in some relation */
+		cl_uint		gone[GPUPREAGG_QUADS];			/* bit j: not folded (all inner: no partner in some relation);
+													 * bit 4 r + j: left / anti relation r did not probe row j */
 		cl_uint		qual_ok[GPUPREAGG_QUADS];		/* bit j: the qual was seen to pass, without an error */
 
 		/* the tile's streamed columns: every relation's key column and the outer columns */
@@ -2301,7 +2373,7 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 			for (int j = 0; j < 4; j++)
 			{
 				bool		live = (full_tile || row0 + j < nitems);
-#define M(r)	live = key_to_slot(P##r, k, j) && live;
+#define M(r)	live = key_verdict(P##r, k, j, live, gone[k]);
 				GPUPREAGG_STAR_REL_LIST(M)
 #undef M
 				if (qual_first && live)
@@ -2328,7 +2400,7 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 #define M(r)	probe(P##r, gone);
 		GPUPREAGG_STAR_REL_LIST(M)
 #undef M
-		/* relation after relation: presence into 'gone', its inner columns into T */
+		/* relation after relation: presence into 'gone' as its join type says, its inner columns into T */
 #define X(attno,colidx,NAME)													\
 		if (((rel::inner_mask >> (colidx)) & 1UL) != 0)								\
 		{																		\
@@ -2356,7 +2428,8 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 				T.v_##attno[k][j] = val;										\
 				nn |= (((flags >> recbit_##attno) & 1u) ? 0u : (1u << j));		\
 			}																	\
-			T.nn_##attno[k] = nn;												\
+			/* (left: the columns of a row without a partner are NULL, whatever slot 0 says) */	\
+			T.nn_##attno[k] = (rel::jointype == 1 ? (nn & ~absent) : nn);		\
 		}
 		auto decode = [&](auto &P)
 		{
@@ -2368,7 +2441,9 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 #pragma unroll
 				for (int j = 0; j < 4; j++)
 					ab |= ((P.w[k][j][0] & 1u) ? 0u : (1u << j));
-				gone[k] |= ab;
+				/* the record's presence bit joins the key's verdict; then the join type's select */
+				const cl_uint absent = (rel::keeps_absent ? (((gone[k] >> rel::absent_shift) & 0xfu) | ab) : ab);
+				gone[k] |= (rel::jointype == 1 ? 0u : rel::jointype == 3 ? (~absent & 0xfu) : ab);
 				STROM_KVAR_LIST(X)
 			}
 		};

@@ -528,7 +528,11 @@ struct preagg_request {
 	Program			   *prog = nullptr;
 	/* joined, lookup: a gpupreagg_joined_map; star: a gpupreagg_star_map (write_joined_map / write_star_map) */
 	std::shared_ptr<std::vector<char>> map;
-	std::string			star_defs;					/* star: the define block 'prog' was built with */
+	/* the define block 'prog' was built with, for checked_program to build again behind GPUPREAGG_CHECKED: a star's,
+	 * and a TYPED one-table lookup's.  EMPTY for an inner one-table lookup, on purpose: its checked retry folds with
+	 * the session's own source (the run-time form of the kernel), as it always did -- lookup_mapping_program fills
+	 * this only where a join type is named, and checked_program relies on that. */
+	std::string			mapping_defs;
 	/* hashed, exact fold (gpupreagg_hashed_exact): 'sess' is a scratch session of this one */
 	strom_gpupreagg	   *exact_parent = nullptr;
 };
@@ -652,6 +656,8 @@ struct fold_mapping {
 	cl_long		key_min[GPUPREAGG_STAR_MAXRELS];
 	cl_uint		nslots[GPUPREAGG_STAR_MAXRELS];
 	cl_ulong	recs[GPUPREAGG_STAR_MAXRELS];			/* device address of the slot records */
+	/* how the relation's presence enters the fold: 0 inner, 1 left, 2 semi, 3 anti (..._lookup_typed) */
+	int32_t		jointype[GPUPREAGG_STAR_MAXRELS] = {};
 };
 
 /*
@@ -660,24 +666,54 @@ struct fold_mapping {
  * (strom_gpupreagg.h: gpupreagg_dense_lookup_body says what that is worth), and only the lookup
  * and merge kernels are built.  One program per distinct mapping (program_with_defines).
  */
-Program *
-lookup_mapping_program(strom_gpupreagg *sess, const fold_mapping &m)
+/* the define block of a one-table mapping (strom_gpupreagg.h: GPUPREAGG_LOOKUP_*); an inner join names
+ * no join type, so its block -- and its program -- is the one it always was.  "" = no valid mapping */
+std::string
+lookup_mapping_defines(int keylen, int reclen, int narrow, uint64_t inner_mask, int jointype)
 {
-	if (getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
-		return nullptr;						/* the run-time form: any mapping, no build */
+	bool	ok = (narrow ? (reclen == 2 || reclen == 4) : (reclen >= 8 && reclen % 4 == 0));
+	if (!ok || !(keylen == 4 || keylen == 8) || jointype < 0 || jointype > 3 || (jointype >= 2 && inner_mask != 0))
+		return "";
 	char		defs[512];
-	snprintf(defs, sizeof(defs),
+	int			n = snprintf(defs, sizeof(defs),
 			 "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_LOOKUP_INNER_MASK 0x%lxUL\n"
 			 "#define GPUPREAGG_LOOKUP_RECLEN %u\n#define GPUPREAGG_LOOKUP_NARROW %u\n"
 			 "#define GPUPREAGG_LOOKUP_KEYLEN %d\n",
-			 (unsigned long)m.inner_mask[0], (unsigned)m.reclen[0], m.narrow[0] ? 1u : 0u, m.key_attlen[0]);
-	return program_with_defines(sess, defs);
+			 (unsigned long)inner_mask, (unsigned)reclen, narrow ? 1u : 0u, keylen);
+	if (jointype != 0)
+		snprintf(defs + n, sizeof(defs) - n, "#define GPUPREAGG_LOOKUP_JOINTYPE %d\n", jointype);
+	return defs;
+}
+
+Program *
+lookup_mapping_program(strom_gpupreagg *sess, const fold_mapping &m, std::string *p_typed_defs, int *p_errcode)
+{
+	/* the run-time form: any INNER mapping, no build (it knows no join type: a typed lookup is always built) */
+	if (m.jointype[0] == 0 && getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
+		return nullptr;
+	/* (the checks of lookup_mapping_defines hold for every mapping build_fold_mapping describes: keys of 4 or 8
+	 * bytes, narrow records of 2 or 4, plain ones of 8, 16, 32 or a multiple of 64 -- hashjoin_table_dimrecs.  An
+	 * inner mapping that failed them would fold by the run-time form, which reads any mapping; a typed one has no
+	 * other kernel and is refused) */
+	std::string	defs = lookup_mapping_defines(m.key_attlen[0], m.reclen[0], m.narrow[0], m.inner_mask[0], m.jointype[0]);
+	if (m.jointype[0] == 0)
+		return (defs.empty() ? nullptr : program_with_defines(sess, defs));
+	if (defs.empty())
+	{
+		*p_errcode = StromError_BadRequestMessage;		/* no valid mapping */
+		return nullptr;
+	}
+	Program	   *prog = program_with_defines(sess, defs);
+	if (!prog)
+		*p_errcode = StromError_OutOfMemory;
+	*p_typed_defs = defs;					/* (checked_program builds it again) */
+	return prog;
 }
 
 /* the define block of a star mapping (strom_gpupreagg.h: GPUPREAGG_STAR_*); "" = no valid mapping */
 std::string
 star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, const int32_t *narrow,
-					 const uint64_t *inner_mask)
+					 const uint64_t *inner_mask, const int32_t *jointype = nullptr)
 {
 	if (nrels < 1 || nrels > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask)
 		return "";
@@ -699,6 +735,15 @@ star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, co
 				 "#define GPUPREAGG_STAR_KEYLEN_%d %d\n#define GPUPREAGG_STAR_INNER_MASK_%d 0x%lxUL\n",
 				 r + 1, reclen[r], r + 1, narrow[r] ? 1 : 0, r + 1, keylen[r], r + 1, (unsigned long)inner_mask[r]);
 		defs += buf;
+		/* (an inner relation names no join type: an all-inner star keeps its block and its program) */
+		int		jt = (jointype ? jointype[r] : 0);
+		if (jt < 0 || jt > 3 || (jt >= 2 && inner_mask[r] != 0))
+			return "";						/* a semi or anti relation serves no column */
+		if (jt != 0)
+		{
+			snprintf(buf, sizeof(buf), "#define GPUPREAGG_STAR_JOINTYPE_%d %d\n", r + 1, jt);
+			defs += buf;
+		}
 	}
 	if (total > GPUPREAGG_STAR_MAXRECBYTES)
 		return "";
@@ -708,9 +753,9 @@ star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, co
 /* star of lookups: the session's source built FOR the mapping, like lookup_mapping_program -- and ALWAYS: the
  * star kernels have no run-time-mapping form (STROM_GPUPREAGG_LOOKUP_GENERIC is the one-table call's) */
 Program *
-star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs)
+star_mapping_program(strom_gpupreagg *sess, const std::string &mapping_defs)
 {
-	return program_with_defines(sess, star_defs);
+	return program_with_defines(sess, mapping_defs);
 }
 
 /*
@@ -723,8 +768,9 @@ star_mapping_program(strom_gpupreagg *sess, const std::string &star_defs)
 Program *
 checked_program(const preagg_request &req)
 {
+	/* (a typed one-table lookup brings its block too: the run-time form of the kernel knows no join type) */
 	return program_with_defines(req.sess, "#define GPUPREAGG_CHECKED 1\n" +
-								(req.kind == PREAGG_STAR ? req.star_defs : std::string()));
+								((req.kind == PREAGG_STAR || req.kind == PREAGG_LOOKUP) ? req.mapping_defs : std::string()));
 }
 
 /*
@@ -2816,7 +2862,7 @@ write_star_map(const fold_mapping &m)
 }	/* namespace */
 
 /*
- * The three fused folds (strom_hip.h): the rows a finished GpuHashJoin produced, straight from its result
+ * The fused folds (strom_hip.h): the rows a finished GpuHashJoin produced, straight from its result
  * pairs (gpupreagg_dense_joined); the join as a lookup inside the aggregate's own pass over the outer chunk,
  * no join request at all (gpupreagg_dense_lookup); a star of such lookups, one table per relation
  * (gpupreagg_dense_lookup_star) -- and a snowflake, which is the lookup or the star it flattens to.  One launch
@@ -2836,13 +2882,13 @@ launch_fused_fold(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jta
 	{
 		/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
 		 * all relations: no define block -- the kernel keeps a row's records in registers) */
-		req.star_defs = star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask);
-		if (req.star_defs.empty())
+		req.mapping_defs = star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask, m.jointype);
+		if (req.mapping_defs.empty())
 		{
 			*p_errcode = StromError_BadRequestMessage;
 			return nullptr;
 		}
-		req.prog = star_mapping_program(sess, req.star_defs);
+		req.prog = star_mapping_program(sess, req.mapping_defs);
 		if (!req.prog)
 		{
 			*p_errcode = StromError_OutOfMemory;
@@ -2852,7 +2898,13 @@ launch_fused_fold(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jta
 	}
 	else if (entry == PREAGG_LOOKUP)
 	{
-		req.prog = lookup_mapping_program(sess, m);
+		int		rc = 0;
+		req.prog = lookup_mapping_program(sess, m, &req.mapping_defs, &rc);
+		if (rc != 0)
+		{
+			*p_errcode = rc;
+			return nullptr;
+		}
 		req.map = write_joined_map(m);
 	}
 	else
@@ -2877,7 +2929,7 @@ static strom_task *
 submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *join_handle,
 					   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
 					   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
-					   strom_done_cb done, void *arg, int *p_errcode)
+					   strom_done_cb done, void *arg, int *p_errcode, const int32_t *jointypes = nullptr)
 {
 	STROM_ABI_TRY
 	int		dummy;
@@ -2888,6 +2940,8 @@ submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *joi
 	*p_errcode = build_fold_mapping(sess, entry, jtask, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids, &m);
 	if (*p_errcode != 0)
 		return nullptr;
+	for (int r = 0; jointypes && r < ntbls; r++)
+		m.jointype[r] = jointypes[r];
 	return launch_fused_fold(sess, entry, jtask, m, outer, done, arg, p_errcode);
 	STROM_ABI_CATCH(nullptr, p_errcode)
 }
@@ -2937,6 +2991,73 @@ strom_submit_gpupreagg_lookup_star(strom_gpupreagg *sess,
 	/* (one relation is the one-table call, its kernel and its error codes) */
 	return submit_gpupreagg_fused(sess, (ntbls == 1 && tbls) ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
 								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode);
+}
+
+extern "C" int
+strom_gpupreagg_lookup_typed_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+									 const int32_t *narrow, const uint64_t *inner_mask, const int32_t *jointypes,
+									 char *buf, size_t buflen)
+{
+	if (ntbls < 1 || ntbls > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask || !jointypes)
+		return -1;
+	/* (one relation: the one-table kernels' block, as the submit call builds it) */
+	std::string	defs = (ntbls == 1 ? lookup_mapping_defines(keylen[0], reclen[0], narrow[0], inner_mask[0], jointypes[0])
+							   : star_mapping_defines(ntbls, keylen, reclen, narrow, inner_mask, jointypes));
+	if (defs.empty() || !buf || defs.size() + 1 > buflen)
+		return -1;
+	memcpy(buf, defs.c_str(), defs.size() + 1);
+	return (int)defs.size();
+}
+
+extern "C" int
+strom_gpupreagg_mapping_defines(strom_gpupreagg *sess, char *buf, size_t buflen)
+{
+	if (!sess)
+		return -1;
+	std::string	all;
+	{
+		std::lock_guard<std::mutex> g(sess->lock);
+		for (auto &kv : sess->lookup_programs)
+			all += kv.first + "\n";
+	}
+	if (buf && all.size() + 1 <= buflen)
+		memcpy(buf, all.c_str(), all.size() + 1);
+	else if (buf)
+		return -1;
+	return (int)all.size();
+}
+
+extern "C" strom_task *
+strom_submit_gpupreagg_lookup_typed(strom_gpupreagg *sess,
+									strom_hashjoin_table *const *tbls, int ntbls, const int32_t *jointypes,
+									strom_dstore *outer,
+									int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+									const int32_t *type_oids,
+									strom_done_cb done, void *arg, int *p_errcode)
+{
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	bool	typed = false;
+	for (int r = 0; jointypes && r >= 0 && r < ntbls && r < GPUPREAGG_STAR_MAXRELS; r++)
+		typed = typed || (jointypes[r] != 0);
+	/* (all inner: the star call -- its code path, its error codes, its programs) */
+	if (jointypes && !typed)
+		return strom_submit_gpupreagg_lookup_star(sess, tbls, ntbls, outer, ncols, src_depth, src_colidx, type_oids,
+												  done, arg, p_errcode);
+	/* a join type outside 0 .. 3; a column asked of a relation that only filters (semi, anti) */
+	bool	ok = (jointypes && ntbls >= 1 && ntbls <= GPUPREAGG_STAR_MAXRELS);
+	for (int r = 0; ok && r < ntbls; r++)
+		ok = (jointypes[r] >= 0 && jointypes[r] <= 3);
+	for (int i = 0; ok && src_depth && i < ncols && i < GPUPREAGG_JOINED_MAXCOLS; i++)
+		ok = !(src_depth[i] >= 1 && src_depth[i] <= ntbls && jointypes[src_depth[i] - 1] >= 2);
+	if (!ok)
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	return submit_gpupreagg_fused(sess, ntbls == 1 ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
+								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode, jointypes);
 }
 
 extern "C" int

@@ -89,6 +89,45 @@ def lookup_star_defines(relations):
     return buf.value.decode()
 
 
+JOINTYPE_NAMES = {"inner": 0, "left": 1, "semi": 2, "anti": 3}
+
+
+def _jointype_codes(jointypes):
+    """join types as the C ABI takes them: names of JOINTYPE_NAMES or integers, as they are (the
+    library refuses a value outside 0 .. 3)"""
+    out = []
+    for jt in jointypes:
+        if isinstance(jt, str):
+            if jt not in JOINTYPE_NAMES:
+                raise ValueError("join type %r: one of %s" % (jt, ", ".join(JOINTYPE_NAMES)))
+            jt = JOINTYPE_NAMES[jt]
+        out.append(int(jt))
+    return np.array(out, dtype=np.int32)
+
+
+def lookup_typed_defines(relations, jointypes):
+    """lookup_star_defines for a mapping with join types (strom_gpupreagg_lookup_typed_defines):
+    relations as there, jointypes one of "inner" | "left" | "semi" | "anti" (or 0 .. 3) per
+    relation.  One relation gives the one-table kernels' block, 2 .. 4 the star's; all inner, the
+    star's text is lookup_star_defines' byte for byte.  ValueError: no valid mapping, a join type
+    outside 0 .. 3, a column under a semi or anti relation."""
+    n = len(relations)
+    jts = _jointype_codes(jointypes)
+    if len(jts) != n:
+        raise ValueError("one join type per relation")
+    keylen = np.array([r[0] for r in relations], dtype=np.int32)
+    reclen = np.array([r[1] for r in relations], dtype=np.int32)
+    narrow = np.array([1 if r[2] else 0 for r in relations], dtype=np.int32)
+    masks = np.array([sum(1 << c for c in r[3]) for r in relations], dtype=np.uint64)
+    buf = ctypes.create_string_buffer(4096)
+    rc = lib.strom_gpupreagg_lookup_typed_defines(n, keylen.ctypes.data, reclen.ctypes.data,
+                                                  narrow.ctypes.data, masks.ctypes.data, jts.ctypes.data,
+                                                  buf, len(buf))
+    if rc < 0:
+        raise ValueError("no typed lookup mapping: %r, %r" % (relations, list(jointypes)))
+    return buf.value.decode()
+
+
 def lookup_snowflake_roots(parents, column_depths):
     """which star a snowflake flattens to (strom_gpupreagg_lookup_snowflake_roots; no device needed):
     parents[d - 1] is 0 for a relation joined on a fact column, p < d for one joined on a column of
@@ -298,6 +337,37 @@ class GpuPreAgg(object):
         if not task:
             raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_star")
         return (task, chunk, (depth, colidx, oids, tbls))
+
+    def submit_lookup_typed(self, joins, jointypes, chunk, columns):
+        """submit_lookup_star with a join type per relation (strom_submit_gpupreagg_lookup_typed):
+        jointypes[d - 1] is "inner" | "left" | "semi" | "anti" (or 0 .. 3).  joins[d - 1] lends an
+        INNER table as in submit_lookup_star -- the join type belongs to this fold, not to the
+        table's program.  A row is folded iff every inner and semi relation has a partner for it
+        and no anti relation has one; a left relation drops no row and its columns are NULL where
+        it has no partner; semi and anti relations serve no column (BadRequest).  The program's
+        qual is the WHERE, after the join.  All "inner" is submit_lookup_star."""
+        depth, colidx, oids = _column_mapping(columns)
+        jts = _jointype_codes(jointypes)
+        if len(jts) != len(joins):
+            raise ValueError("one join type per relation")
+        tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpupreagg_lookup_typed(self.session, tbls, len(joins),
+                                                       jts.ctypes.data if len(jts) else None, chunk.handle,
+                                                       len(columns), depth.ctypes.data, colidx.ctypes.data,
+                                                       oids.ctypes.data, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_typed")
+        return (task, chunk, (depth, colidx, oids, tbls, jts))
+
+    def mapping_defines(self):
+        """the define blocks of the programs this session has built for fused folds so far
+        (strom_gpupreagg_mapping_defines): a list of texts as lookup_typed_defines gives them"""
+        need = lib.strom_gpupreagg_mapping_defines(self.session, None, 0)
+        buf = ctypes.create_string_buffer(max(1, need) + 1)
+        if need < 0 or lib.strom_gpupreagg_mapping_defines(self.session, buf, len(buf)) < 0:
+            raise runtime.StromError(-1, "strom_gpupreagg_mapping_defines")
+        return [b + "\n" for b in buf.value.decode().split("\n\n") if b]
 
     def submit_lookup_snowflake(self, joins, parents, chunk, columns, link_types=None):
         """fact JOIN d1 JOIN d2 ... GROUP BY where a relation may be keyed by ANOTHER relation's column

@@ -648,7 +648,8 @@ strom_task *strom_submit_gpupreagg_lookup(strom_gpupreagg *sess,
  * requirements above or lives on another device, a hashed session, a session without a domain, a
  * text / character(n) variable of the program that is not mapped to depth 0, under its own type
  * (STROM_TEXTOID / STROM_BPCHARNOID), onto an outer column with attlen -1 (no relation serves a
- * text column: slot records hold fixed-width values), a key that is not 4 or 8 bytes wide, and for ntbls >= 2 a
+ * text VARIABLE: slot records hold fixed-width values; a relation's text column is served as int4
+ * ids, a coded column made by strom_textdict_encode_table, mapped under int4), a key that is not 4 or 8 bytes wide, and for ntbls >= 2 a
  * relation whose slot record is longer than 16 bytes or records that total more than 32 bytes
  * over all relations (the kernel holds a row's records of all relations in registers): the
  * caller then goes through the plain join and strom_hashjoin_project_column().
@@ -860,6 +861,13 @@ strom_devprog_key strom_textdict_program(strom_textdict *dict);
 /* forget every key (keycomp keeps no state between queries; this is the next query's dictionary) */
 void		strom_textdict_reset(strom_textdict *dict);
 void		strom_textdict_release(strom_textdict *dict);
+/* a DIMENSION's text column under a dictionary, as int4 ids by slot of its hash table, served by
+ * every fused fold like an int4 column of the relation: strom_textdict_encode_table, declared and
+ * described in a file of its own.  (reset and release end the epoch of the ids such columns hold.)
+ * NOTE: tests/test_textdict_cpu.py pins the set of strom_textdict_* entry points declared in THIS file;
+ * an entry point declared in the included file is outside that pin and is checked by
+ * tests/test_dim_text_lookup_cpu.py instead -- a further one needs a check of its own there. */
+#include "strom_textdict_table.h"
 
 /* ------------------------------------------------------------------ *
  * GROUP BY text across sessions and GPUs: one numbering for several dictionaries

@@ -221,6 +221,7 @@ PROTOTYPES = {
     "strom_textdict_program": (c_uint64, [c_void_p]),
     "strom_textdict_reset": (None, [c_void_p]),
     "strom_textdict_release": (None, [c_void_p]),
+    "strom_textdict_encode_table": (c_int, [c_void_p, c_void_p, c_int]),
     "strom_keyunion_absorb": (c_void_p, [c_void_p, c_void_p, c_size_t, c_void_p, c_uint32,
                                          ctypes.POINTER(c_int)]),
     "strom_keyunion_absorb_dict": (c_void_p, [c_void_p, c_void_p, ctypes.POINTER(c_int)]),

@@ -393,11 +393,13 @@ static_assert(sizeof(hashjoin_build_stats) == 24, "hashjoin_build_stats");
 /* inner columns by slot, packed (hashjoin_build_dimrec_kernel), their ranges
  * (hashjoin_dimrec_minmax_kernel) and the narrow form (hashjoin_dimrec_narrow_kernel) */
 #define HASHJOIN_DIMREC_MAXCOLS	16
+#define HASHJOIN_DIMREC_CODED	(-2)	/* a coded column of the table (int4 ids of a text column, by slot) */
 struct hashjoin_dimrec_spec {
 	cl_uint		ncols;
 	cl_uint		reclen;
 	struct {
-		cl_int		col;			/* inner column, 0-based */
+		cl_int		col;			/* inner column, 0-based; HASHJOIN_DIMREC_CODED: no column of the tuple, the
+									 * field is laid out NULL and filled by hashjoin_patch_dimrec_kernel */
 		cl_int		attlen;
 		cl_uint		offset;			/* of the value inside the record */
 		cl_uint		__pad;
@@ -490,6 +492,20 @@ static_assert(sizeof(textdict_ctl) == 32, "textdict_ctl");
 static_assert(sizeof(textdict_entry) == 16, "textdict_entry");
 static_assert(sizeof(textdict_newkey) == 8, "textdict_newkey");
 static_assert(sizeof(textdict_args) == 104, "textdict_args");
+/* a text column of a hash table's one relation (DIRECT index, unique keys) under the dictionary, by SLOT
+ * of the table (textdict_table_*): the second argument of those kernels, next to a textdict_args whose
+ * row_slot / newkeys are tbl_nslots long and whose "rows" are the table's slots */
+struct textdict_table_args {
+	cl_ulong	kmhash;				/* the table's kern_multihash image: read-only for the whole call */
+	cl_ulong	hjidx;				/* its hashjoin_index */
+	cl_ulong	datum_off;			/* cl_ulong[tbl_nslots]: the slot's checked datum, bytes from kmhash;
+									 * 0 = no row in the slot, or a NULL column */
+	cl_ulong	out_ids;			/* emit: cl_int[tbl_nslots] */
+	cl_ulong	out_isnull;			/* emit: cl_uchar[tbl_nslots], 1 = absent slot or NULL datum (id 0) */
+	cl_uint		tbl_nslots;			/* hashjoin_index_rel.nslots, <= 2^31 */
+	cl_int		colidx;				/* the relation's column, attlen -1 */
+};
+static_assert(sizeof(textdict_table_args) == 48, "textdict_table_args");
 
 /* ---------------------------------------------------------------------- *
  * union of key dictionaries (strom_textdict.h: keyunion_*, textdict.cpp)

@@ -1777,6 +1777,8 @@ hashjoin_build_dimrec_kernel(const kern_multihash *kmhash, const hashjoin_index 
 	for (cl_uint i = 0; i < ncols; i++)
 	{
 		cl_int	col = spec->c[i].col;
+		if (col == HASHJOIN_DIMREC_CODED && spec->c[i].attlen == 4)
+			continue;			/* laid out NULL here, filled by hashjoin_patch_dimrec_kernel */
 		if (col < 0 || col >= (cl_int)kht->ncols || kht->colmeta[col].attlen != spec->c[i].attlen)
 		{
 			if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -1795,7 +1797,7 @@ hashjoin_build_dimrec_kernel(const kern_multihash *kmhash, const hashjoin_index 
 			const char *addr = NULL;
 			cl_int		attlen = spec->c[i].attlen;
 			char	   *out = rec + spec->c[i].offset;
-			if (off != 0)
+			if (off != 0 && spec->c[i].col != HASHJOIN_DIMREC_CODED)
 			{
 				const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + off);
 				addr = kern_get_datum_tuple(kht->colmeta, &ent->htup, spec->c[i].col);
@@ -1811,6 +1813,30 @@ hashjoin_build_dimrec_kernel(const kern_multihash *kmhash, const hashjoin_index 
 				flags |= (2u << i);
 		}
 		*(cl_uint *)rec = flags;
+	}
+}
+
+/*
+ * a CODED column into the records hashjoin_build_dimrec_kernel laid out: the int4 ids of a text
+ * column of this relation under a key dictionary, by slot (strom_textdict.h: textdict_table_emit
+ * writes ids[] / isnull[] in the form of hashjoin_build_dimcol_kernel).  The field at 'offset' and
+ * its NULL bit 'nullbit' of the flags word; an absent slot has isnull 1 and stays as it was laid
+ * out.  Runs after the build kernel on the same stream, before anyone reads the records.
+ */
+extern "C" __global__ void
+__launch_bounds__(256)
+hashjoin_patch_dimrec_kernel(char *recs, cl_uint reclen, cl_uint nslots, cl_uint offset, cl_uint nullbit,
+							 const cl_int *ids, const cl_uchar *isnull)
+{
+	for (cl_uint s = blockIdx.x * blockDim.x + threadIdx.x; s < nslots; s += gridDim.x * blockDim.x)
+	{
+		char	   *rec = recs + (size_t)reclen * s;
+
+		if (isnull[s] == 0)
+		{
+			*(cl_int *)(rec + offset) = ids[s];
+			*(cl_uint *)rec &= ~(1u << nullbit);
+		}
 	}
 }
 

@@ -37,7 +37,11 @@
  *   textdict_rebuild  one key per lane: entries -> a cleared slot array (growth, and the way back
  *                     from a failed probe: the entries are what a probe never touches)
  *
- * The second half of the file (keyunion_*) lets a dictionary absorb the keys of other dictionaries
+ * textdict_table_* are the same three steps over the rows of a HASH TABLE, by slot: a dimension's text
+ * column becomes int4 ids kept with the table (a coded column), which the fused folds serve like any
+ * int4 column of the relation.
+ *
+ * The last part of the file (keyunion_*) lets a dictionary absorb the keys of other dictionaries
  * with ids that do not depend on timing, and rewrites encoded id columns through the id maps that
  * come of it: what sessions of several shards need before their tables can be merged.
  */
@@ -477,6 +481,341 @@ textdict_rebuild(textdict_args a)
 			}
 			if (!placed)
 				errcode = StromError_DataStoreNoSpace;
+		}
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+/* ================================================================ *
+ * a DIMENSION's text column as a coded column: the dictionary walks the rows of a hash table (one
+ * relation, DIRECT index, unique keys: what hashjoin_build_dimrec_kernel walks) by SLOT and leaves
+ * ids[slot] / isnull[slot], the form hashjoin_build_dimcol_kernel writes.  The fused folds then
+ * serve the ids like any int4 column of the relation; no text datum enters a slot record.
+ *
+ *   textdict_table_offsets  one slot per lane: slot array -> kern_hashentry -> kern_get_datum_tuple,
+ *                           the datum checked as textdict_row_datum checks a row's; its offset from
+ *                           the table image into datum_off[slot], 0 for an absent slot or a NULL
+ *   textdict_table_probe    the walk of textdict_probe written out a third time (see keyunion_probe
+ *                           for why not one definition); a PENDING word names a SLOT INDEX of the
+ *                           table, and "index -> address" is one load from datum_off[], as it is one
+ *                           load from a chunk's values[].  The table image and datum_off[] are
+ *                           complete before the launch and never written during it: whatever a lane
+ *                           finds in a slot of the dictionary, the bytes to compare are readable at
+ *                           once.  No lane waits for another.  Many slots carry the same key (1e6
+ *                           customers, 25 nations): "found under a PENDING or settled word"
+ *   textdict_table_settle   textdict_settle with the datum read through datum_off[]
+ *   textdict_table_emit     ids[slot] (int4), isnull[slot] (one byte); id 0 with isnull 1 for an
+ *                           absent slot and for a NULL datum alike
+ * ================================================================ */
+STROM_DEVICE cl_ulong
+textdict_table_datum(const textdict_table_args &t, cl_uint slot)
+{
+	cl_ulong	off = ((const cl_ulong *)t.datum_off)[slot];
+
+	return off != 0 ? t.kmhash + off : 0UL;
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+textdict_table_offsets(textdict_table_args t, textdict_args a)
+{
+	const kern_multihash *kmhash = (const kern_multihash *)t.kmhash;
+	const hashjoin_index *hjidx = (const hashjoin_index *)t.hjidx;
+	const kern_hashtable *kht = KERN_HASHTABLE(kmhash, 0);
+	const hashjoin_index_rel *ir = &hjidx->rel[0];
+	const cl_uint *slots = (const cl_uint *)((const char *)hjidx + ir->slots_off);
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	cl_ulong   *datum_off = (cl_ulong *)t.datum_off;
+	const cl_uint nslots = t.tbl_nslots;
+	const cl_ulong length = kht->length;
+	const cl_ulong kht_at = (cl_ulong)((const char *)kht - (const char *)kmhash);
+	/* not a varlena column (the table lies, or the caller does): never followed as a datum */
+	const bool	badcol = (t.colidx < 0 || t.colidx >= (cl_int)kht->ncols || kht->colmeta[t.colidx].attlen != -1 ||
+						  ir->nslots != nslots);
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < nslots; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		slot = base + threadIdx.x;
+		cl_ulong	at = 0;
+		cl_int		rowerr = StromError_Success;
+		cl_uint		off = (slot < nslots && !badcol ? slots[slot] : 0u);
+
+		if (slot < nslots && badcol)
+			rowerr = StromError_DataStoreCorruption;
+		else if (off != 0)
+		{
+			/* the entry and its tuple inside the table, then the datum by its own length */
+			const kern_hashentry *ent = (const kern_hashentry *)((const char *)kht + off);
+			const char *addr = NULL;
+
+			if ((cl_ulong)off + offsetof(kern_hashentry, htup) + HEAPTUPLE_HEADER_FIXED > length ||
+				ent->t_len < HEAPTUPLE_HEADER_FIXED ||
+				(cl_ulong)off + offsetof(kern_hashentry, htup) + ent->t_len > length)
+				rowerr = StromError_DataStoreCorruption;
+			else
+				addr = kern_get_datum_tuple(kht->colmeta, &ent->htup, (cl_uint)t.colidx);
+			if (addr != NULL)
+			{
+				cl_ulong	doff = (cl_ulong)(addr - (const char *)kht);
+				cl_uchar	b0 = (doff < length ? ((const cl_uchar *)addr)[0] : 0);
+
+				/* (the rest of a 2-byte external tag or a 4-byte header lies inside the table as well) */
+				if (doff >= length || doff + (b0 == 0x01 ? 2 : ((b0 & 0x01) ? 1 : 4)) > length)
+					rowerr = StromError_DataStoreCorruption;
+				else
+				{
+					cl_uint		size = strom_varsize_any(addr);
+
+					if (doff + size > length || size < ((b0 & 0x01) ? 1u : 4u))
+						rowerr = StromError_DataStoreCorruption;
+					else if (b0 == 0x01 || (b0 & 0x03) == 0x02)
+						rowerr = StromError_CpuReCheck;		/* external, or compressed */
+					else
+						at = kht_at + doff;
+				}
+			}
+		}
+		if (slot < nslots)
+			datum_off[slot] = at;
+		STROM_SET_ERROR(&errcode, rowerr);
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+textdict_table_probe(textdict_table_args t, textdict_args a)
+{
+	cl_ulong   *slots = (cl_ulong *)a.slots;
+	const textdict_entry *entries = (const textdict_entry *)a.entries;
+	const char *heap = (const char *)a.heap;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	cl_uint	   *row_slot = (cl_uint *)a.row_slot;
+	textdict_newkey *newkeys = (textdict_newkey *)a.newkeys;
+	const cl_uint nrows = t.tbl_nslots;
+	const cl_uint mask = a.nslots - 1;
+	const bool	blank_padded = (a.blank_padded != 0);
+	cl_int		errcode = StromError_Success;
+
+	/* blockDim is whole waves and 'base' is the block's: every lane of a wave takes every turn */
+	for (cl_uint base = blockIdx.x * blockDim.x; base < nrows; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		row = base + threadIdx.x;			/* a slot of the TABLE */
+		cl_uint		myslot = TEXTDICT_NO_SLOT;			/* a slot of the DICTIONARY */
+		cl_uint		size = 0;
+		bool		won = false;
+		cl_int		rowerr = StromError_Success;
+		cl_ulong	datum = (row < nrows ? textdict_table_datum(t, row) : 0UL);
+
+		if (datum != 0)
+		{
+			cl_int		len;
+			const cl_uchar *key = textdict_key_bytes(datum, blank_padded, &len);
+			cl_ulong	h = textdict_hash(datum, blank_padded);
+			cl_ulong	tag = textdict_tag(h);
+			cl_uint		s = (cl_uint)h & mask;
+			bool		placed = false;
+
+			size = strom_varsize_any((const char *)datum);
+			for (cl_uint step = 0; step < a.nslots; step++, s = (s + 1) & mask)
+			{
+				cl_ulong	w = textdict_load_slot(slots, s);
+
+				/* a look, not a wait (see textdict_probe) */
+				if ((step & 63) == 16 &&
+					__hip_atomic_load(&ctl->toofull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)
+					break;
+				if (w == 0)
+				{
+					cl_ulong	mine = tag | TEXTDICT_PENDING | row;
+
+					if (__hip_atomic_compare_exchange_strong((textdict_slot_p)(slots + s), &w, mine,
+															 __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+															 __HIP_MEMORY_SCOPE_AGENT))
+					{
+						won = placed = true;
+						break;
+					}
+					/* lost: 'w' is the winner's word, looked at like any occupied slot */
+				}
+				if ((w & (TEXTDICT_OCCUPIED | TEXTDICT_TAG_MASK)) != tag)
+					continue;
+				cl_ulong	other = 0;
+				if (w & TEXTDICT_PENDING)
+				{
+					/* a slot of this table, checked by textdict_table_offsets before this launch */
+					if ((cl_uint)w < nrows)
+						other = textdict_table_datum(t, (cl_uint)w);
+				}
+				else if ((cl_uint)w < a.nkeys)
+					other = (cl_ulong)(heap + entries[(cl_uint)w].off);
+				if (other == 0)
+				{
+					rowerr = StromError_SanityCheckViolation;	/* a word no launch writes */
+					break;
+				}
+				cl_int		olen;
+				const cl_uchar *okey = textdict_key_bytes(other, blank_padded, &olen);
+				if (strom_bytes_equal(key, len, okey, olen))
+				{
+					placed = true;
+					break;
+				}
+			}
+			if (placed)
+				myslot = s;
+			else if (rowerr == StromError_Success)
+				rowerr = StromError_DataStoreNoSpace;
+		}
+		if (row < nrows)
+			row_slot[row] = myslot;
+		/* the claims of a wave: one add for their count, one for their bytes */
+		strom_lanemask_t winners = __ballot(won);
+		if (winners != 0)
+		{
+			cl_uint		bytes = textdict_wave_sum(won ? (cl_uint)STROM_INTALIGN(size) : 0u);
+			int			leader = __ffsll((long long)winners) - 1;
+			cl_uint		k0 = 0;
+
+			if ((int)strom_lane_id() == leader)
+			{
+				k0 = atomicAdd(&ctl->nnew, (cl_uint)__popcll(winners));
+				atomicAdd((unsigned long long *)&ctl->heap_need, (unsigned long long)bytes);
+			}
+			k0 = __shfl(k0, leader, STROM_WAVE);
+			/* past half full: say so NOW (see textdict_probe) */
+			if ((int)strom_lane_id() == leader &&
+				2 * ((cl_ulong)a.nkeys + k0 + (cl_uint)__popcll(winners)) > (cl_ulong)a.nslots)
+				__hip_atomic_store(&ctl->toofull, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (won)
+			{
+				cl_uint		k = k0 + strom_mbcnt(winners);
+				if (k < nrows)		/* a slot wins once at most */
+				{
+					newkeys[k].slot = myslot;
+					newkeys[k].row = row;
+				}
+			}
+		}
+		STROM_SET_ERROR(&errcode, rowerr);
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+textdict_table_settle(textdict_table_args t, textdict_args a)
+{
+	cl_ulong   *slots = (cl_ulong *)a.slots;
+	textdict_entry *entries = (textdict_entry *)a.entries;
+	char	   *heap = (char *)a.heap;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	const textdict_newkey *newkeys = (const textdict_newkey *)a.newkeys;
+	const cl_uint nrows = t.tbl_nslots;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < a.nnew; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		k = base + threadIdx.x;
+		bool		valid = (k < a.nnew);
+		cl_uint		slot = 0, row = 0, size = 0, asize = 0;
+		const char *from = NULL;
+
+		if (valid)
+		{
+			slot = newkeys[k].slot;
+			row = newkeys[k].row;
+			if (slot >= a.nslots || row >= nrows)
+			{
+				errcode = StromError_SanityCheckViolation;
+				valid = false;
+			}
+		}
+		if (valid)
+		{
+			from = (const char *)textdict_table_datum(t, row);	/* checked by textdict_table_offsets */
+			if (from == NULL)
+			{
+				errcode = StromError_SanityCheckViolation;		/* a slot without a datum claims nothing */
+				valid = false;
+			}
+		}
+		if (valid)
+		{
+			size = strom_varsize_any(from);
+			asize = (cl_uint)STROM_INTALIGN(size);
+		}
+		/* a wave's share of the heap with one add: inclusive prefix sum over the lanes */
+		cl_uint		lane = strom_lane_id();
+		cl_uint		upto = asize;
+#pragma unroll
+		for (int d = 1; d < STROM_WAVE; d <<= 1)
+		{
+			cl_uint o = __shfl_up(upto, d, STROM_WAVE);
+			if (lane >= (cl_uint)d)
+				upto += o;
+		}
+		cl_uint		total = __shfl(upto, STROM_WAVE - 1, STROM_WAVE);
+		cl_ulong	wave_at = 0;
+		if (lane == 0 && total != 0)
+			wave_at = atomicAdd((unsigned long long *)&ctl->heap_cursor, (unsigned long long)total);
+		wave_at = __shfl(wave_at, 0, STROM_WAVE);
+		if (!valid)
+			continue;
+		cl_ulong	at = a.heap_usage + wave_at + (upto - asize);
+		if (at + asize > a.heap_size)
+		{
+			errcode = StromError_SanityCheckViolation;		/* the host sized the heap by heap_need */
+			continue;
+		}
+		char	   *to = heap + at;
+		cl_uint		i = 0;
+		for (; i + 8 <= size; i += 8)
+			((__attribute__((address_space(1))) textdict_unaligned_u64 *)(to + i))->v = strom_load_u64((const cl_uchar *)from + i);
+		for (; i < size; i++)
+			to[i] = from[i];
+		cl_uint		id = a.nkeys + k;
+		cl_ulong	h = textdict_hash((cl_ulong)from, a.blank_padded != 0);
+		entries[id].hash = h;
+		entries[id].off = at;
+		__hip_atomic_store((textdict_slot_p)(slots + slot), textdict_tag(h) | id,
+						   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	textdict_writeback_status(&ctl->status, errcode);
+}
+
+extern "C" __global__ void __launch_bounds__(TEXTDICT_BLOCK)
+textdict_table_emit(textdict_table_args t, textdict_args a)
+{
+	const cl_ulong *slots = (const cl_ulong *)a.slots;
+	textdict_ctl *ctl = (textdict_ctl *)a.ctl;
+	const cl_uint *row_slot = (const cl_uint *)a.row_slot;
+	cl_int	   *out_ids = (cl_int *)t.out_ids;
+	cl_uchar   *out_isnull = (cl_uchar *)t.out_isnull;
+	const cl_uint nrows = t.tbl_nslots;
+	cl_int		errcode = StromError_Success;
+
+	for (cl_uint base = blockIdx.x * blockDim.x; base < nrows; base += gridDim.x * blockDim.x)
+	{
+		cl_uint		row = base + threadIdx.x;
+
+		if (row < nrows)
+		{
+			cl_uint		s = row_slot[row];
+			cl_int		id = 0;
+			bool		isnull = true;
+
+			if (s != TEXTDICT_NO_SLOT)
+			{
+				cl_ulong	w = (s < a.nslots ? slots[s] : 0UL);
+				if ((w & TEXTDICT_OCCUPIED) == 0 || (w & TEXTDICT_PENDING) != 0 || (cl_uint)w >= a.nkeys)
+					errcode = StromError_SanityCheckViolation;
+				else
+				{
+					id = (cl_int)(cl_uint)w;
+					isnull = false;
+				}
+			}
+			out_ids[row] = id;
+			out_isnull[row] = (isnull ? 1 : 0);
 		}
 	}
 	textdict_writeback_status(&ctl->status, errcode);

@@ -40,6 +40,16 @@ struct strom_hashjoin_table {
 	/* narrow form of a record set (same key), built on the first lookup that can take it;
 	 * reclen 0 = tried, does not fit */
 	std::map<std::string, dimrec_narrow> dimrecs_narrow;
+	/* CODED columns (strom_textdict_encode_table): the int4 ids of text column 'col' under the dictionary
+	 * (serial, epoch), by slot, in the form of dimcols.  coded[i] is column rel_ncols[0] + i of the relation
+	 * to hashjoin_table_dimrecs; an entry is never removed, one whose epoch is stale is refused there */
+	struct coded_column {
+		int			col = 0;
+		uint64_t	dict_serial = 0, dict_epoch = 0;
+		cl_int	   *ids = nullptr;
+		cl_uchar   *isnull = nullptr;
+	};
+	std::vector<coded_column> coded;
 	/* a snowflake below this table flattened into its slot records (hashjoin_snowflake_dimrecs),
 	 * kept with the ROOT: key = the subtree as text, every descendant by its serial number (not
 	 * its address: a released table's is used again) */
@@ -310,6 +320,11 @@ strom_hashjoin_table_release(strom_hashjoin_table *tbl)
 	{
 		dev->pool.release(kv.second.first);
 		dev->pool.release(kv.second.second);
+	}
+	for (auto &cc : tbl->coded)
+	{
+		dev->pool.release(cc.ids);
+		dev->pool.release(cc.isnull);
 	}
 	for (auto &kv : tbl->dimrecs)
 		dev->pool.release(kv.second.first);
@@ -1122,6 +1137,95 @@ strom::hashjoin_table_dimcol(strom_hashjoin_table *tbl, int col, int attlen, voi
 	return 0;
 }
 
+/*
+ * text column 'colidx' of the table's relation becomes a CODED column: ids under 'dict' by slot, kept
+ * with the table.  The dictionary does the work (textdict.cpp: textdict_encode_table_slots); the table
+ * owns the arrays and remembers the dictionary by (serial, epoch).
+ */
+extern "C" int
+strom_textdict_encode_table(strom_textdict *dict, strom_hashjoin_table *tbl, int colidx)
+{
+	STROM_ABI_TRY
+	int			dict_dindex = -1;
+	uint64_t	serial = 0, epoch = 0;
+
+	if (!dict || !tbl || textdict_identity(dict, &dict_dindex, &serial, &epoch) != 0)
+		return -(int)StromError_BadRequestMessage;
+	if (tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique ||
+		tbl->dev->dindex != dict_dindex || colidx < 0 || colidx >= (int)tbl->rel_ncols[0])
+		return -(int)StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(tbl->dim_lock);
+	size_t		at = tbl->coded.size();
+	for (size_t i = 0; i < tbl->coded.size(); i++)
+	{
+		auto   &cc = tbl->coded[i];
+		if (cc.col != colidx)
+			continue;
+		bool	current = textdict_epoch_is_current(cc.dict_serial, cc.dict_epoch);
+		if (cc.dict_serial == serial && current)
+			return (int)tbl->rel_ncols[0] + (int)i;		/* done before: nothing is launched, no key added */
+		if (cc.dict_serial != serial && current)
+			return -(int)StromError_BadRequestMessage;	/* one numbering per column at a time */
+		at = i;												/* its dictionary was reset or is gone: coded anew */
+	}
+	if (at == tbl->coded.size() && at >= 1024)
+		return -(int)StromError_BadRequestMessage;
+	Device	   *dev = tbl->dev;
+	cl_uint		nslots = tbl->head.rel[0].nslots;
+	(void)hipSetDevice(dev->hip_id);
+	cl_int	   *d_ids = (cl_int *)dev->pool.alloc(sizeof(cl_int) * (size_t)nslots + 16);
+	cl_uchar   *d_isnull = (cl_uchar *)dev->pool.alloc((size_t)nslots + 16);
+	int			rc = (!d_ids || !d_isnull) ? StromError_OutOfMemory
+		: textdict_encode_table_slots(dict, tbl->d_kmhash, tbl->d_index, nslots, colidx, d_ids, d_isnull);
+	if (rc != 0)
+	{
+		if (d_ids) dev->pool.release(d_ids);
+		if (d_isnull) dev->pool.release(d_isnull);
+		return -rc;
+	}
+	if (at == tbl->coded.size())
+		tbl->coded.emplace_back();
+	else
+	{
+		/* the records this table made from the old ids go with them: their keys carry the ended epoch,
+		 * nobody can ask for them again, and a table that lives across many resets would pile them up.  A
+		 * fold queued before the reset may still read them: every stream of the device first.  (Composed
+		 * records kept with ANOTHER table, the root of a snowflake over this one, stay until that table
+		 * is released: stale too, and as unreachable.) */
+		for (auto st : dev->streams)
+			(void)hipStreamSynchronize(st);
+		std::string	stale = "~" + std::to_string(tbl->coded[at].dict_serial) + "." +
+			std::to_string(tbl->coded[at].dict_epoch) + ",";
+		for (auto it = tbl->dimrecs.begin(); it != tbl->dimrecs.end(); )
+		{
+			if (it->first.find(stale) == std::string::npos)
+			{
+				++it;
+				continue;
+			}
+			auto	nit = tbl->dimrecs_narrow.find(it->first);
+			if (nit != tbl->dimrecs_narrow.end())
+			{
+				if (nit->second.recs)
+					dev->pool.release(nit->second.recs);
+				tbl->dimrecs_narrow.erase(nit);
+			}
+			dev->pool.release(it->second.first);
+			it = tbl->dimrecs.erase(it);
+		}
+		dev->pool.release(tbl->coded[at].ids);
+		dev->pool.release(tbl->coded[at].isnull);
+	}
+	auto   &cc = tbl->coded[at];
+	cc.col = colidx;
+	cc.dict_serial = serial;
+	cc.dict_epoch = epoch;
+	cc.ids = d_ids;
+	cc.isnull = d_isnull;
+	return (int)tbl->rel_ncols[0] + (int)at;
+	STROM_ABI_CATCH(-(int)StromError_OutOfMemory, (int *)nullptr)
+}
+
 namespace {
 
 /*
@@ -1266,12 +1370,29 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 		return StromError_BadRequestMessage;
 	unsigned	reclen = spec.reclen;
 	std::string	key;
+	int			coded_at[HASHJOIN_DIMREC_MAXCOLS];
+	std::lock_guard<std::mutex> g(tbl->dim_lock);
 	for (int i = 0; i < n; i++)
 	{
 		offsets[i] = spec.c[i].offset;
-		key += std::to_string(cols[i]) + ":" + std::to_string(attlens[i]) + ",";
+		key += std::to_string(cols[i]) + ":" + std::to_string(attlens[i]);
+		/* a coded column (strom_textdict_encode_table) is int4 ids by slot, not a column of the tuples: the
+		 * build kernel lays its field out NULL and the patch kernel below fills it.  Its dictionary and
+		 * epoch are part of the key: ids of another numbering are other records.  An index past the
+		 * relation's columns that is no coded column goes to the build kernel as ever, which refuses it. */
+		int		ci = cols[i] - (int)tbl->rel_ncols[0];
+		coded_at[i] = -1;
+		if (ci >= 0 && ci < (int)tbl->coded.size() && attlens[i] == 4)
+		{
+			const auto &cc = tbl->coded[ci];
+			if (!textdict_epoch_is_current(cc.dict_serial, cc.dict_epoch))
+				return StromError_BadRequestMessage;		/* stale ids: the dictionary was reset or released */
+			coded_at[i] = ci;
+			spec.c[i].col = HASHJOIN_DIMREC_CODED;
+			key += "~" + std::to_string(cc.dict_serial) + "." + std::to_string(cc.dict_epoch);
+		}
+		key += ",";
 	}
-	std::lock_guard<std::mutex> g(tbl->dim_lock);
 	auto	it = tbl->dimrecs.find(key);
 	if (it == tbl->dimrecs.end())
 	{
@@ -1297,6 +1418,27 @@ strom::hashjoin_table_dimrecs(strom_hashjoin_table *tbl, int n, const int *cols,
 				  hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, dev->streams[0], args, nullptr) == hipSuccess &&
 				  hipMemcpyAsync(&failed, a_failed, sizeof(cl_uint), hipMemcpyDeviceToHost, dev->streams[0]) == hipSuccess &&
 				  hipStreamSynchronize(dev->streams[0]) == hipSuccess))
+				failed = 1;
+			/* the coded columns' ids and NULL bits into their fields: queued behind the build kernel, one
+			 * wait for all of them */
+			hipFunction_t fn_patch = nullptr;
+			bool		patched = false;
+			for (int i = 0; !failed && i < n; i++)
+			{
+				if (coded_at[i] < 0)
+					continue;
+				if (!fn_patch)
+					fn_patch = tbl->prog->get_function(dev, "hashjoin_patch_dimrec_kernel", &errcode);
+				cl_uint		a_reclen = reclen, a_off = spec.c[i].offset, a_bit = 1u + (cl_uint)i;
+				const void *a_ids = tbl->coded[coded_at[i]].ids;
+				const void *a_null = tbl->coded[coded_at[i]].isnull;
+				void	   *pargs[] = { &a_recs, &a_reclen, &nslots, &a_off, &a_bit, &a_ids, &a_null };
+				if (!fn_patch ||
+					hipModuleLaunchKernel(fn_patch, grid, 1, 1, 256, 1, 1, 0, dev->streams[0], pargs, nullptr) != hipSuccess)
+					failed = 1;
+				patched = true;
+			}
+			if (patched && hipStreamSynchronize(dev->streams[0]) != hipSuccess)
 				failed = 1;
 		}
 		if (d_spec) dev->pool.release(d_spec);
@@ -1559,6 +1701,21 @@ strom::hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, 
 	for (int k = 0; k < ncols; k++)
 		if (cols[k].rel < 1 || cols[k].rel > ntbls || !below[cols[k].rel])
 			return StromError_BadRequestMessage;
+	/* a coded column of any relation of the tree (strom_textdict_encode_table): composed records hold its
+	 * ids, which are good under one epoch of its dictionary only -- part of the key, and a stale one is
+	 * refused here as hashjoin_table_dimrecs refuses it (a hit below never gets that far) */
+	for (int k = 0; k < ncols; k++)
+	{
+		strom_hashjoin_table *t = tbls[cols[k].rel - 1];
+		std::lock_guard<std::mutex> g(t->dim_lock);
+		int		ci = cols[k].col - (int)t->rel_ncols[0];
+		if (ci < 0 || ci >= (int)t->coded.size() || cols[k].attlen != 4)
+			continue;
+		if (!textdict_epoch_is_current(t->coded[ci].dict_serial, t->coded[ci].dict_epoch))
+			return StromError_BadRequestMessage;
+		key += "~" + std::to_string(k) + "=" + std::to_string(t->coded[ci].dict_serial) + "." +
+			std::to_string(t->coded[ci].dict_epoch);
+	}
 	/* never two tables' dim_lock at once: look, flatten without the root's lock (each relation's
 	 * records are fetched under its own), then take the root's again to keep the result */
 	bool		hit;

@@ -285,6 +285,16 @@ int			hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, c
 									   void **p_recs, unsigned *p_reclen, dimrec_narrow *narrow);
 int			hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 									   int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual = nullptr);
+/* textdict.cpp, for the table that keeps a coded column (gpuhashjoin.cpp: strom_textdict_encode_table).
+ * A dictionary is known to its tables by (serial, epoch): the serial is its own for the life of the
+ * process, the epoch counts its resets; a released dictionary has no current epoch at all. */
+int			textdict_identity(strom_textdict *dict, int *p_dindex, uint64_t *p_serial, uint64_t *p_epoch);
+bool		textdict_epoch_is_current(uint64_t serial, uint64_t epoch);
+/* the varlena column colidx of the one relation of the table image (d_kmhash, d_index: DIRECT, unique
+ * keys, tbl_nslots slots) under dict: d_ids[slot] (int4) / d_isnull[slot] (one byte).  Blocks; an error
+ * leaves the dictionary as it was. */
+int			textdict_encode_table_slots(strom_textdict *dict, const void *d_kmhash, const void *d_index,
+										cl_uint tbl_nslots, int colidx, void *d_ids, void *d_isnull);
 /* gpupreagg.cpp, for the RCCL merge (parallel.cpp) */
 struct gpupreagg_merge_plan {
 	preagg_merge_spec spec;

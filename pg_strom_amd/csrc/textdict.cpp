@@ -44,15 +44,38 @@ struct strom_textdict {
 	uint64_t	union_ns[6] = {0, 0, 0, 0, 0, 0};
 	/* the program the last encode ran: TEXTDICT_BLOCK / TEXTDICT_HASH_BITS are part of its text */
 	strom_devprog_key program = 0;
+	/* who this dictionary is to the tables that hold coded columns under it (textdict_encode_table_slots):
+	 * a number no other dictionary of the process gets, and the count of its resets.  Ids are only
+	 * good under the (serial, epoch) they were made under. */
+	uint64_t	serial = 0;
+	uint64_t	epoch = 1;
 };
 
 namespace {
 
+/* serial -> epoch of every living dictionary: what a table asks by NUMBER, so that a coded column
+ * whose dictionary was reset or released is found stale without touching the handle */
+std::mutex &
+epoch_lock(void)
+{
+	static std::mutex &m = *new std::mutex();
+	return m;
+}
+
+std::map<uint64_t, uint64_t> &
+epoch_registry(void)
+{
+	static std::map<uint64_t, uint64_t> &r = *new std::map<uint64_t, uint64_t>();
+	return r;
+}
+
 enum { K_PROBE = 0, K_SETTLE, K_EMIT, K_REBUILD,
+	   K_TOFFSETS, K_TPROBE, K_TSETTLE, K_TEMIT,
 	   K_UPROBE, K_UCOUNT, K_UOFFSETS, K_USETTLE, K_UEMIT, K_RECODE, K_NFUNCS };
 enum { U_PROBE = 0, U_RANKS, U_SETTLE, U_EMIT, U_REBUILD, U_RECODE };
 const char *const kernel_names[K_NFUNCS] = {
 	"textdict_probe", "textdict_settle", "textdict_emit", "textdict_rebuild",
+	"textdict_table_offsets", "textdict_table_probe", "textdict_table_settle", "textdict_table_emit",
 	"keyunion_probe", "keyunion_count", "keyunion_offsets", "keyunion_settle", "keyunion_emit", "keyunion_recode" };
 
 /* the fixed program; the two knobs are part of its text (as build() pre-builds it) */
@@ -228,12 +251,24 @@ struct Encoder {
 		return 0;
 	}
 
-	/* one key column: ids into out_values / out_notnull; *p_nnull = its NULL rows */
+	/* one key column of a chunk: ids into out_values / out_notnull; *p_nnull = its NULL rows */
 	int encode_column(strom_textdict *dict, strom_dstore *src, cl_uint colidx, cl_uint *row_slot,
 					  textdict_newkey *newkeys, void *out_values, void *out_notnull, cl_uint *p_nnull)
 	{
 		const void *a_src = src->devptr;
-		cl_uint		nrows = src->head.nitems;
+		return encode_rows(dict, K_PROBE, &a_src, src->head.nitems, colidx, row_slot, newkeys,
+						   out_values, out_notnull, p_nnull);
+	}
+
+	/*
+	 * the host policy of an encode, for both sources of rows: the kernels 'first' (probe), first + 1
+	 * (settle), first + 2 (emit) take (*src_arg, textdict_args) -- a chunk and its rows, or a
+	 * textdict_table_args and the table's slots
+	 */
+	int encode_rows(strom_textdict *dict, int first, void *src_arg, cl_uint nrows, cl_uint colidx, cl_uint *row_slot,
+					textdict_newkey *newkeys, void *out_values, void *out_notnull, cl_uint *p_nnull)
+	{
+		void	   *a_src_p = src_arg;
 		textdict_ctl ctl;
 		int			rc;
 
@@ -243,11 +278,11 @@ struct Encoder {
 			a.row_slot = (cl_ulong)(uintptr_t)row_slot;
 			a.newkeys = (cl_ulong)(uintptr_t)newkeys;
 			a.colidx = colidx;
-			void	   *args[] = { &a_src, &a };
+			void	   *args[] = { a_src_p, &a };
 
 			if (hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), stream) != hipSuccess)
 				return StromError_HipInternal;
-			if ((rc = launch(&dict->kern_ns[K_PROBE], K_PROBE, grid_for(nrows), args)) != 0 || (rc = read_ctl(dict, &ctl)) != 0)
+			if ((rc = launch(&dict->kern_ns[K_PROBE], first, grid_for(nrows), args)) != 0 || (rc = read_ctl(dict, &ctl)) != 0)
 				return rc;
 			size_t	keys_after = (size_t)dict->nkeys + ctl.nnew;
 			/* no place found, or the claims took the table past half full; a row error goes first */
@@ -302,8 +337,8 @@ struct Encoder {
 			a.newkeys = (cl_ulong)(uintptr_t)newkeys;
 			a.colidx = colidx;
 			a.nnew = nnew;
-			void	   *args[] = { &a_src, &a };
-			rc = launch(&dict->kern_ns[K_SETTLE], K_SETTLE, grid_for(nnew), args);
+			void	   *args[] = { a_src_p, &a };
+			rc = launch(&dict->kern_ns[K_SETTLE], first + 1, grid_for(nnew), args);
 		}
 		if (rc == 0)
 		{
@@ -312,8 +347,8 @@ struct Encoder {
 			a.row_slot = (cl_ulong)(uintptr_t)row_slot;
 			a.out_values = (cl_ulong)(uintptr_t)out_values;
 			a.out_notnull = (cl_ulong)(uintptr_t)out_notnull;
-			void	   *args[] = { &a_src, &a };
-			if ((rc = launch(&dict->kern_ns[K_EMIT], K_EMIT, grid_for(nrows), args)) == 0 && (rc = read_ctl(dict, &ctl)) == 0)
+			void	   *args[] = { a_src_p, &a };
+			if ((rc = launch(&dict->kern_ns[K_EMIT], first + 2, grid_for(nrows), args)) == 0 && (rc = read_ctl(dict, &ctl)) == 0)
 				rc = ctl.status;				/* settle or emit met a word no launch writes */
 		}
 		if (rc != 0)
@@ -422,6 +457,12 @@ strom_textdict_create(int type_oid, uint32_t nkeys_hint, int dindex, int *p_errc
 		delete dict;
 		return nullptr;
 	}
+	{
+		static uint64_t next_serial = 0;
+		std::lock_guard<std::mutex> g(epoch_lock());
+		dict->serial = ++next_serial;
+		epoch_registry()[dict->serial] = dict->epoch;
+	}
 	return dict;
 	STROM_ABI_CATCH(nullptr, p_errcode)
 }
@@ -439,6 +480,11 @@ strom_textdict_reset(strom_textdict *dict)
 	if (!dev)
 		return;
 	(void)hipSetDevice(dev->hip_id);
+	{
+		/* the ids of every coded column made so far name keys that are about to go */
+		std::lock_guard<std::mutex> g(epoch_lock());
+		epoch_registry()[dict->serial] = ++dict->epoch;
+	}
 	dict->nkeys = 0;
 	dict->heap_usage = 0;
 	(void)hipMemsetAsync(dict->slots, 0, sizeof(cl_ulong) * (size_t)dict->nslots, dev->streams[0]);
@@ -450,6 +496,10 @@ strom_textdict_release(strom_textdict *dict)
 {
 	if (!dict)
 		return;
+	{
+		std::lock_guard<std::mutex> g(epoch_lock());
+		epoch_registry().erase(dict->serial);
+	}
 	Device *dev = get_device(dict->dindex);
 	if (dev)
 	{
@@ -693,6 +743,89 @@ strom_textdict_encode(strom_textdict *const *dicts, const int32_t *key_colidx, i
 	if (!result && d_dst) dev->pool.release(d_dst);
 	return result;
 	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+/* ------------------------------------------------------------------ *
+ * a dimension's text column as a coded column (devlib/strom_textdict.h: textdict_table_*), the
+ * dictionary's half of strom_textdict_encode_table (gpuhashjoin.cpp owns the table and the arrays)
+ * ------------------------------------------------------------------ */
+int
+strom::textdict_identity(strom_textdict *dict, int *p_dindex, uint64_t *p_serial, uint64_t *p_epoch)
+{
+	if (!dict)
+		return StromError_BadRequestMessage;
+	*p_dindex = dict->dindex;
+	*p_serial = dict->serial;
+	*p_epoch = dict->epoch;
+	return 0;
+}
+
+bool
+strom::textdict_epoch_is_current(uint64_t serial, uint64_t epoch)
+{
+	std::lock_guard<std::mutex> g(epoch_lock());
+	auto	it = epoch_registry().find(serial);
+	return it != epoch_registry().end() && it->second == epoch;
+}
+
+/*
+ * One encode over the slots of a table: offsets (every datum checked; an error ends the call before
+ * the dictionary is touched) -> the policy of an encode of a chunk (Encoder::encode_rows), its rows
+ * being the table's slots.  d_ids / d_isnull: tbl_nslots long, the caller's.
+ */
+int
+strom::textdict_encode_table_slots(strom_textdict *dict, const void *d_kmhash, const void *d_index,
+								   cl_uint tbl_nslots, int colidx, void *d_ids, void *d_isnull)
+{
+	Device *dev = dict ? get_device(dict->dindex) : nullptr;
+	if (!dev)
+		return dict ? StromError_ServerNotReady : StromError_BadRequestMessage;
+	if (tbl_nslots < 1 || tbl_nslots > (1u << 31))
+		return StromError_BadRequestMessage;
+	(void)hipSetDevice(dev->hip_id);
+	Encoder	enc;
+	strom_devprog_key progkey = 0;
+	int		rc = enc.open(dev, K_REBUILD, K_TEMIT, &progkey);
+	if (rc != 0)
+		return rc;
+	cl_ulong   *d_datum_off = (cl_ulong *)dev->pool.alloc(sizeof(cl_ulong) * (size_t)tbl_nslots);
+	cl_uint	   *d_row_slot = (cl_uint *)dev->pool.alloc(sizeof(cl_uint) * (size_t)tbl_nslots);
+	textdict_newkey *d_newkeys = (textdict_newkey *)dev->pool.alloc(sizeof(textdict_newkey) * (size_t)tbl_nslots);
+	rc = (!d_datum_off || !d_row_slot || !d_newkeys) ? StromError_OutOfMemory : 0;
+	if (rc == 0)
+	{
+		textdict_table_args t;
+		textdict_args a = enc.base_args(dict);
+		textdict_ctl ctl;
+		void	   *args[] = { &t, &a };
+		cl_uint		nnull = 0;
+
+		memset(&t, 0, sizeof(t));
+		t.kmhash = (cl_ulong)(uintptr_t)d_kmhash;
+		t.hjidx = (cl_ulong)(uintptr_t)d_index;
+		t.datum_off = (cl_ulong)(uintptr_t)d_datum_off;
+		t.out_ids = (cl_ulong)(uintptr_t)d_ids;
+		t.out_isnull = (cl_ulong)(uintptr_t)d_isnull;
+		t.tbl_nslots = tbl_nslots;
+		t.colidx = colidx;
+		memset(dict->kern_ns, 0, sizeof(dict->kern_ns));
+		dict->program = progkey;
+		enc.rebuild_ns = &dict->kern_ns[K_REBUILD];
+		/* (the offsets pass is part of finding the rows' keys: its time goes to the probe's account) */
+		if (hipMemsetAsync(dict->ctl, 0, sizeof(textdict_ctl), enc.stream) != hipSuccess)
+			rc = StromError_HipInternal;
+		else if ((rc = enc.launch(&dict->kern_ns[K_PROBE], K_TOFFSETS, enc.grid_for(tbl_nslots), args)) == 0 &&
+				 (rc = enc.read_ctl(dict, &ctl)) == 0)
+			rc = ctl.status;
+		if (rc == 0)
+			rc = enc.encode_rows(dict, K_TPROBE, &t, tbl_nslots, (cl_uint)colidx, d_row_slot, d_newkeys,
+								 nullptr, nullptr, &nnull);
+	}
+	(void)hipStreamSynchronize(enc.stream);
+	if (d_datum_off) dev->pool.release(d_datum_off);
+	if (d_row_slot) dev->pool.release(d_row_slot);
+	if (d_newkeys) dev->pool.release(d_newkeys);
+	return rc;
 }
 
 /* ------------------------------------------------------------------ *

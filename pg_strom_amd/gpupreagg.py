@@ -295,7 +295,8 @@ class GpuPreAgg(object):
         STROM_RESULTS_ON_DEVICE) not yet collected; columns as in join_to_column.
         The join's device results pass to this request.  A text / character(n) variable of the
         program must be a column of 'chunk': mapped at depth 0, as "text" / "character", onto a
-        varlena column (BadRequest otherwise; a dimension serves fixed-width columns only)."""
+        varlena column (BadRequest otherwise; a dimension serves fixed-width columns, its text column
+        as the int4 ids of a coded column: TextDictionary.encode_table)."""
         depth, colidx, oids = _column_mapping(columns)
         err = ctypes.c_int(0)
         task = lib.strom_submit_gpupreagg_joined(self.session, join_pending[0], join.table, chunk.handle,
@@ -310,8 +311,9 @@ class GpuPreAgg(object):
         is a lookup in the aggregate's own pass over the resident COLUMN chunk; 'join' only
         lends its hash table.  columns as in join_to_column.  A text / character(n) variable of
         the program (in the qual, in an aggregate's argument) must be a fact column: mapped at depth
-        0, as "text" / "character", onto a varlena column of 'chunk' -- BadRequest otherwise, a
-        dimension serves fixed-width columns only.  An unreadable (compressed / external) datum in
+        0, as "text" / "character", onto a varlena column of 'chunk' -- BadRequest otherwise.  A
+        dimension's text column is served as ids: TextDictionary.encode_table(join, col) returns the
+        index of a coded column, mapped as (1, index + 1, "int4").  An unreadable (compressed / external) datum in
         a row that has a partner sends the chunk back (status 2, nothing folded)."""
         depth, colidx, oids = _column_mapping(columns)
         err = ctypes.c_int(0)

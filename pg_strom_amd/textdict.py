@@ -74,6 +74,18 @@ class TextDictionary(object):
             raise runtime.StromError(err.value, "strom_textdict_encode")
         return runtime.DeviceStore(h, store.nitems)
 
+    def encode_table(self, join, col):
+        """text / character(n) column 'col' (0-based) of the one relation of join's hash table (DIRECT
+        index, unique keys) becomes a CODED column of the table: int4 ids under this dictionary, by
+        slot (strom_textdict_encode_table).  Returns its 0-based column index (>= the relation's own
+        columns): the fused folds serve it like any int4 column of the relation -- mapped as
+        (depth, index + 1, "int4").  A second call returns the same index.  The dictionary must
+        outlive the table, unreset."""
+        rc = lib.strom_textdict_encode_table(self.handle, join.table, int(col))
+        if rc < 0:
+            raise runtime.StromError(-rc, "strom_textdict_encode_table")
+        return rc
+
     def image(self):
         """the keys as they lie in the dictionary: (heap bytes, offsets[id] of each complete datum) --
         what another dictionary absorbs, on this rank or on another"""
@@ -340,6 +352,36 @@ def group_by_text(chunks, text_keys, spec, carry_cols, hashed=False, row_maps=No
         if own:
             for d in dicts:
                 d.release()
+
+
+def group_by_dimension_text(chunks, join, text_col, kind, spec, columns, dictionary=None):
+    """SELECT dim.t, agg(..) FROM fact JOIN dim GROUP BY dim.t, the loop a backend would write: the
+    dimension's text column is encoded ONCE, at table time, and every chunk is one lookup fold.
+
+    chunks     resident COLUMN chunks of the fact table
+    join       a begun GpuHashJoin whose table is the dimension (one relation, DIRECT, unique keys)
+    text_col   0-based text / character(n) column of the dimension; kind "text" | "character"
+    spec       GpuPreAgg IR whose FIRST key is (key (var K int4)), K the virtual column of the ids
+    columns    the mapping as submit_lookup takes it, with None in the place of that virtual column:
+               it becomes (1, coded index + 1, "int4")
+    Returns (PartialRows, [keys of the id column: bytes, None for the NULL group])."""
+    own = dictionary is None
+    d = TextDictionary(kind) if own else dictionary
+    agg = GpuPreAgg(spec)
+    try:
+        coded = d.encode_table(join, text_col)
+        columns = [(1, coded + 1, "int4") if c is None else c for c in columns]
+        agg.begin([(0, max(d.num_keys, 1))])
+        for chunk in chunks:
+            status, _ = agg.collect(agg.submit_lookup(join, chunk, columns))
+            if status != 0:
+                raise runtime.StromError(status, "GpuPreAgg lookup fold")
+        pr = agg.fetch()
+        return pr, ids_to_keys(pr, [d])[0]
+    finally:
+        agg.end()
+        if own:
+            d.release()
 
 
 def ids_to_keys(pr, dicts):

@@ -547,12 +547,15 @@ strom_dstore *strom_hashjoin_project_column(strom_task *join_task, strom_hashjoi
  *   device first, so they come after every join task of this table submitted before them, waited
  *   for or not.  Join tasks submitted afterwards are the caller's business.
  * BadRequestMessage, nothing launched: any of these on a table without tracking (_tracked_depth
- *   and _matches_length answer 0); strom_submit_gpupreagg_lookup / _lookup_star / _lookup_snowflake
- *   on a TRACKED table (they probe without running the join program and would leave every flag
+ *   and _matches_length answer 0); strom_submit_gpupreagg_lookup / _lookup_star / _lookup_snowflake / _lookup_typed
+ *   / _lookup_tracked on a TRACKED table (they probe without running the join program and would leave every flag
  *   clear); strom_submit_gpupreagg_joined stays allowed for the JOIN tasks of such a table -- the join
  *   ran and flagged -- and refuses a task of the unmatched pass: its records name no outer row.
- * Still out: a tracked relation that is not the last; tracked tables in the fused lookup folds; a
- *   run on more than one GPU (two tables on one device stand in for two ranks).
+ *   RIGHT and FULL joins in the fused lookup folds are asked of the FOLD, over an untracked inner table:
+ *   strom_submit_gpupreagg_lookup_tracked, with flags by SLOT that the session owns.
+ * Still out: a tracked relation that is not the last; (track_matches) tables in the fused lookup folds (their
+ *   flags are addressed by entry, the folds' by slot); a run on more than one GPU (two tables on one device
+ *   stand in for two ranks).
  */
 strom_task *strom_submit_gpuhashjoin_unmatched(strom_hashjoin_table *tbl, kern_hashjoin *khashjoin,
 											   uint32_t flags, strom_done_cb done, void *arg,
@@ -697,6 +700,7 @@ int			strom_gpupreagg_lookup_star_defines(int ntbls, const int32_t *keylen, cons
  * STROM_LOOKUP_STAR_MAXRELS relations are the star kernels (GPUPREAGG_STAR_JOINTYPE_<d>).
  * BadRequest, and nothing is launched: jointypes NULL or a value outside 0 .. 3, a virtual column
  * mapped to a semi or anti relation, and everything strom_submit_gpupreagg_lookup_star refuses.
+ * RIGHT and FULL joins of one of the relations: strom_submit_gpupreagg_lookup_tracked, below.
  */
 strom_task *strom_submit_gpupreagg_lookup_typed(strom_gpupreagg *sess,
 												strom_hashjoin_table *const *tbls, int ntbls,
@@ -717,7 +721,91 @@ int			strom_gpupreagg_lookup_typed_defines(int ntbls, const int32_t *keylen, con
 												 const int32_t *jointypes, char *buf, size_t buflen);
 
 /*
- * The define blocks of the programs this session has built FOR a mapping so far (one-table, star, typed; a
+ * ... and RIGHT and FULL joins: "SELECT dim.name, count(fact.k), sum(fact.x) FROM fact RIGHT JOIN dim ON
+ * fact.k = dim.k GROUP BY dim.name" -- every member of the dimension, also those without facts.  The join's
+ * own idiom (above: RIGHT = inner + track_matches, FULL = left + the same), asked of the FOLD: ONE relation
+ * of the mapping may be TRACKED, 'tracked' is its number 1 .. ntbls; tracked + inner is a RIGHT join of that
+ * relation, tracked + left a FULL join.  tbls[] are the untracked INNER tables the typed call takes (a table
+ * built with (track_matches) stays refused: its flags are addressed by entry, these by slot).
+ *   Join order.  The result is (fact JOIN the other relations, by their join types) RIGHT | FULL JOIN
+ *     tracked: the tracked relation is joined LAST, and the relations no longer commute with it.
+ *   Per chunk.  strom_submit_gpupreagg_lookup_tracked folds exactly what _lookup_typed folds for the same
+ *     jointypes[]; tracking changes no row of it.  On the side the kernel notes which slots of the tracked
+ *     table had a partner: slot s is MATCHED when some fact row of some chunk (1) has a key that is not NULL
+ *     and lies inside the table's key range, (2) finds s present, and (3) survives every other relation --
+ *     every inner and semi relation has a partner for it, no anti relation has one; a left relation never
+ *     drops a row.  The WHERE does not decide a match: the aggregate program's (qual ...) is applied after
+ *     the join, so a partner row that the qual rejects still matches its slot -- also a qual over fact
+ *     columns alone (a tracked program does not evaluate it before the probe), which matters for quals that
+ *     are not strict: "fact RIGHT JOIN dim ... WHERE fact.a IS NULL" is the anti-join from the right.  An
+ *     error does not decide a match either: a chunk that ends CpuReCheck is not folded, but its flags are
+ *     complete -- they are facts of the keys, and the kernel walks every row -- and a retry of the chunk
+ *     sets the same flags again.
+ *   The flags.  One byte per slot of the tracked table (0 unmatched, 1 matched), in device memory, zeroed
+ *     when made, OWNED BY THE SESSION: slot records are shared between sessions and read-only, what matched
+ *     is a fact of one query.  They are made by the first tracked request or by the unmatched call, bound
+ *     to (table, tracked position, slot count) from then on, and freed with the session.  Plain byte loads
+ *     and stores, test before set: no device atomics, no bit per slot (a byte store is no read-modify-write).
+ *   The unmatched pass.  strom_submit_gpupreagg_lookup_unmatched takes the same mapping WITHOUT a chunk, after
+ *     the last one: one row per slot of the tracked table that is present and not flagged.  The columns the
+ *     tracked relation serves come from its slot record, with the record's own NULL bits; every other virtual
+ *     column -- fact columns, text ones included, other relations' columns -- is NULL.  The row goes through
+ *     the program's qual and is folded into the session like any row; qual and row errors are that task's
+ *     status (CpuReCheck: nothing of the pass is folded).  It reads no chunk, takes no key width and depends
+ *     on no fact column's width.  With no fold before it (an empty fact table) it emits every present slot.
+ *     STROM_GPUPREAGG_UNMATCHED_MAX_GRID caps the work-groups that walk the slots (read on every call).
+ *   Dimension rows with a NULL key have no slot, so the pass could never emit them: a table that holds one
+ *     is refused as the tracked one (BadRequest; found once per table, entries against occupied slots), and
+ *     the caller takes the join's RIGHT path, which does emit them.
+ *   Ordering.  The unmatched call and the _matches_fetch / _merge / _reset calls synchronise the device
+ *     first, like the join's: they come after every fold that has been LAUNCHED.  A fold whose program is
+ *     still being built is parked and launched later -- wait for the folds (strom_task_wait) first.
+ *   The seam.  strom_gpupreagg_lookup_matches_length / _fetch / _merge are what
+ *     strom_hashjoin_table_matches_* are to the join: every rank or shard folds its part of the fact rows, one
+ *     of them ORs the others' flag images in (_merge: 'len' must be _length and every byte 0 or 1, BadRequest
+ *     and nothing merged otherwise), merges the partial rows as ever and runs the unmatched pass.
+ *     strom_gpupreagg_lookup_reset_matches clears the flags and re-arms the pass (a rescan).
+ * tracked == 0 IS strom_submit_gpupreagg_lookup_typed: its code path, its error codes, its programs.
+ * BadRequest, and nothing is launched: everything the typed call refuses; tracked outside 0 .. ntbls; a
+ * tracked semi or anti relation; a table with a NULL-key entry as the tracked one; a tracked request whose
+ * (table, position) is not the one the session's flags are bound to; a second unmatched call, or a tracked
+ * fold after the unmatched pass, without a reset; _matches_fetch / _merge / _reset on a session without flags
+ * (_matches_length answers 0).  strom_submit_gpupreagg_lookup_snowflake offers no tracking.
+ */
+strom_task *strom_submit_gpupreagg_lookup_tracked(strom_gpupreagg *sess,
+												  strom_hashjoin_table *const *tbls, int ntbls,
+												  const int32_t *jointypes,	/* [ntbls] 0 inner, 1 left, 2 semi, 3 anti */
+												  int tracked,				/* 0: none; d: relation d, RIGHT (inner) / FULL (left) */
+												  strom_dstore *outer,
+												  int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+												  const int32_t *type_oids,
+												  strom_done_cb done, void *arg, int *p_errcode);
+strom_task *strom_submit_gpupreagg_lookup_unmatched(strom_gpupreagg *sess,
+													strom_hashjoin_table *const *tbls, int ntbls,
+													const int32_t *jointypes, int tracked,	/* 1 .. ntbls */
+													int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+													const int32_t *type_oids,
+													strom_done_cb done, void *arg, int *p_errcode);
+/*
+ * strom_gpupreagg_lookup_typed_defines plus 'tracked': 0 returns the typed text byte for byte, otherwise
+ * the block ends in one more line -- "#define GPUPREAGG_LOOKUP_TRACK 1" for the one-table block,
+ * "#define GPUPREAGG_STAR_TRACK_REL d" for the star.  -1 also for tracked out of range or naming a semi /
+ * anti relation.  _unmatched_defines: the block of the unmatched pass, which holds the tracked relation's
+ * record facts only (length, narrow form, served-column mask).
+ */
+int			strom_gpupreagg_lookup_tracked_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+												   const int32_t *narrow, const uint64_t *inner_mask,
+												   const int32_t *jointypes, int tracked, char *buf, size_t buflen);
+int			strom_gpupreagg_lookup_unmatched_defines(int reclen, int narrow, uint64_t inner_mask,
+													 char *buf, size_t buflen);
+size_t		strom_gpupreagg_lookup_matches_length(strom_gpupreagg *sess);
+int			strom_gpupreagg_lookup_matches_fetch(strom_gpupreagg *sess, void *buf, size_t len);
+int			strom_gpupreagg_lookup_matches_merge(strom_gpupreagg *sess, const void *buf, size_t len);
+int			strom_gpupreagg_lookup_reset_matches(strom_gpupreagg *sess);
+
+/*
+ * The define blocks of the programs this session has built FOR a mapping so far (one-table, star, typed,
+ * tracked, the unmatched pass; a
  * checked retry's begins with GPUPREAGG_CHECKED), each followed by an empty line: what a request's tables came
  * to -- record length and form, served columns, join types -- for a planner's log or a test.  Returns the
  * length of the text (buf NULL: only that), or -1 if it does not fit buflen.

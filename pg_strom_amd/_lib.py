@@ -150,6 +150,19 @@ PROTOTYPES = {
     "strom_gpupreagg_lookup_typed_defines": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                         ctypes.c_char_p, c_size_t]),
     "strom_gpupreagg_mapping_defines": (c_int, [c_void_p, ctypes.c_char_p, c_size_t]),
+    "strom_submit_gpupreagg_lookup_tracked": (c_void_p, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         ctypes.POINTER(c_int)]),
+    "strom_submit_gpupreagg_lookup_unmatched": (c_void_p, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                           ctypes.POINTER(c_int)]),
+    "strom_gpupreagg_lookup_tracked_defines": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                          ctypes.c_char_p, c_size_t]),
+    "strom_gpupreagg_lookup_unmatched_defines": (c_int, [c_int, c_int, ctypes.c_uint64, ctypes.c_char_p, c_size_t]),
+    "strom_gpupreagg_lookup_matches_length": (c_size_t, [c_void_p]),
+    "strom_gpupreagg_lookup_matches_fetch": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "strom_gpupreagg_lookup_matches_merge": (c_int, [c_void_p, c_void_p, c_size_t]),
+    "strom_gpupreagg_lookup_reset_matches": (c_int, [c_void_p]),
     "strom_submit_gpupreagg_lookup_snowflake": (c_void_p, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                            ctypes.POINTER(c_int)]),

@@ -168,8 +168,15 @@ struct gpupreagg_joined_map {
 	cl_uint		nshift[GPUPREAGG_JOINED_MAXCOLS];
 	cl_uint		nmask[GPUPREAGG_JOINED_MAXCOLS];
 	cl_long		nmin[GPUPREAGG_JOINED_MAXCOLS];
+	/* a TRACKED lookup (RIGHT / FULL: GPUPREAGG_LOOKUP_TRACK) and gpupreagg_dense_lookup_unmatched: the
+	 * session's matched flags of this table, one byte per slot (0 unmatched, 1 matched); 0 otherwise */
+	cl_ulong	matches;
+	/* gpupreagg_dense_lookup_unmatched: the work-groups of a role that walk the slots (the others
+	 * only store their empty slab); 0: all of them */
+	cl_uint		unmatched_wgs;
+	cl_uint		__pad;
 };
-static_assert(sizeof(gpupreagg_joined_map) == 2600, "gpupreagg_joined_map");
+static_assert(sizeof(gpupreagg_joined_map) == 2616, "gpupreagg_joined_map");
 
 /*
  * the virtual joined relation of gpupreagg_dense_lookup_star / _packed_lookup_star: a star of
@@ -203,8 +210,10 @@ struct gpupreagg_star_map {
 		cl_uint		nmask;
 		cl_long		nmin;
 	} c[GPUPREAGG_JOINED_MAXCOLS];
+	/* the matched flags of the TRACKED relation (GPUPREAGG_STAR_TRACK_REL), one byte per slot of it; 0: none */
+	cl_ulong	matches;
 };
-static_assert(sizeof(gpupreagg_star_map) == 2216, "gpupreagg_star_map");
+static_assert(sizeof(gpupreagg_star_map) == 2224, "gpupreagg_star_map");
 
 /* key range of one chunk (gpupreagg_keyrange), read back by the host */
 struct gpupreagg_keyrange_t {

@@ -1586,6 +1586,35 @@ gpupreagg_ablate_sink(const strom_kvars &KV)
 }
 #endif
 
+/*
+ * One served column out of a slot record (hashjoin_build_dimrec_kernel, hashjoin_dimrec_narrow_kernel),
+ * for the one-table fold, the star and the unmatched pass alike.  w0 is the record's first word -- the
+ * flags word, or the whole NARROW record: value = nmin + field -- and w1 .. w3 the rest of a record of up
+ * to 16 bytes (0 where the record ends sooner), all in registers; a longer record is read at 'rec'.
+ * Every argument but the words is uniform, so the selects are scalar.
+ */
+template <typename VAL_T>
+__device__ __forceinline__ VAL_T
+gpupreagg_dimrec_value(bool narrow, cl_uint reclen, cl_uint w0, cl_uint w1, cl_uint w2, cl_uint w3,
+					   const char *rec, cl_uint recoff, cl_uint nshift, cl_uint nmask, cl_long nmin)
+{
+	VAL_T		val;
+
+	if (narrow)
+		val = (VAL_T)(nmin + (cl_long)((w0 >> nshift) & nmask));
+	else if (reclen <= 16)
+	{
+		cl_uint		wi = recoff >> 2;
+		cl_uint		lo = (wi == 1 ? w1 : wi == 2 ? w2 : w3);
+		cl_uint		hi = (wi == 2 ? w3 : 0u);
+		cl_ulong	bits = (((cl_ulong)hi << 32) | lo) >> ((recoff & 3u) * 8u);
+		__builtin_memcpy(&val, &bits, sizeof(val));
+	}
+	else
+		val = *(const VAL_T *)(rec + recoff);
+	return val;
+}
+
 template <typename KEY_T, bool PACKED>
 __device__ __forceinline__ void
 gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
@@ -1687,6 +1716,26 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 	constexpr int	jointype = 0;
 #endif
 	constexpr bool	keeps_absent = (jointype == 1 || jointype == 3);	/* left, anti: a partner-less row may be folded */
+	/*
+	 * A TRACKED relation (GPUPREAGG_LOOKUP_TRACK; with inner a RIGHT join of the table, with left a FULL
+	 * one): the fold is the untracked one row for row, and the kernel also notes which slots had a
+	 * partner -- one byte per slot at jmap->matches, owned by the session, for the unmatched pass
+	 * (gpupreagg_dense_lookup_unmatched) after the last chunk.  A slot is matched by a row that lies in
+	 * the chunk, has a key inside the table and finds the slot present; what the qual says of the row
+	 * does not count (the WHERE comes after the join), so a tracked program has no qual-first.  The
+	 * flag is tested before it is set, with a plain load issued next to the probe, and set with a
+	 * plain byte store: no read-modify-write, nothing atomic; a stale 0 (the XCDs' L2s are not
+	 * coherent) costs one more store of the same 1.  Rows that are not probed read flag 0 as they
+	 * read slot 0 and never store.
+	 */
+#if defined(GPUPREAGG_LOOKUP_TRACK)
+#if !defined(GPUPREAGG_LOOKUP_INNER_MASK) || (defined(GPUPREAGG_LOOKUP_JOINTYPE) && GPUPREAGG_LOOKUP_JOINTYPE >= 2)
+#error "GPUPREAGG_LOOKUP_TRACK: an inner or left relation, in a program built for its mapping"
+#endif
+	constexpr bool	tracked = true;
+#else
+	constexpr bool	tracked = false;
+#endif
 #define X(attno,colidx,NAME)													\
 	const bool	inner_##attno = LOOKUP_INNER(colidx);								\
 	const cl_uint recoff_##attno = strom_uniform((cl_uint)jmap->c[colidx].dimvalues);	\
@@ -1723,7 +1772,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 #define X(attno,colidx,NAME)	inner_mask |= (inner_##attno ? (1UL << colidx) : 0UL);
 	STROM_KVAR_LIST(X)
 #undef X
-	const bool	qual_first = ((GPUPREAGG_QUAL_VARMASK & inner_mask) == 0 && GPUPREAGG_QUAL_VARMASK != 0);
+	const bool	qual_first = (!tracked && (GPUPREAGG_QUAL_VARMASK & inner_mask) == 0 && GPUPREAGG_QUAL_VARMASK != 0);
+	cl_uchar   *matches = (tracked ? LOOKUP_PTR((cl_uchar *)jmap->matches) : (cl_uchar *)NULL);
 	bool		any_nulls = (keynulls != NULL);		/* wave-uniform: picks the bitmap-free loader */
 #define X(attno,colidx,NAME)	any_nulls = any_nulls || (nul_##attno != NULL);
 	STROM_KVAR_LIST(X)
@@ -1797,13 +1847,20 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 	KEY_T		keyq[GPUPREAGG_QUADS][4], keyq_next[GPUPREAGG_QUADS][4];
 	cl_uint		keynn[GPUPREAGG_QUADS], keynn_next[GPUPREAGG_QUADS];
 
-	if (wg_in_split < ntiles)
+	/* (a tracked program has no next-tile prefetch, like the star's: the rows' slots and their flags live from
+	 * the probe to the stores, and the register file does not hold them next to a second tile --
+	 * profiles/lookup_tracked_resources.txt) */
+	constexpr bool	prefetch = !tracked;
+	if (prefetch && wg_in_split < ntiles)
 		load_tile(wg_in_split, T, keyq, keynn);
 	for (cl_uint tile = wg_in_split; tile < ntiles; tile += wgs_per_split)
 	{
 		cl_uint		tile_base = tile * GPUPREAGG_TILE_ROWS;
 		bool		full_tile = (tile_base + GPUPREAGG_TILE_ROWS <= nitems);
-		bool		more = (tile + wgs_per_split < ntiles);		/* (uniform) */
+		bool		more = (prefetch && tile + wgs_per_split < ntiles);		/* (uniform) */
+
+		if (!prefetch)
+			load_tile(tile, T, keyq, keynn);
 
 		/*
 		 * every lookup of the tile is issued before the first is used (a
@@ -1850,6 +1907,7 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 			}
 		}
 		cl_uint	words[GPUPREAGG_QUADS][4][4];	/* records of 8 / 16 bytes: the whole record, fetched in ONE load */
+		cl_uchar mflag[GPUPREAGG_QUADS][4];		/* tracked: the slot's matched flag as it was (its address needs no record) */
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
@@ -1857,6 +1915,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 			for (int j = 0; j < 4; j++)
 			{
 				const char *rec = recs + (size_t)reclen * slot[k][j];
+				if (tracked)
+					mflag[k][j] = LOOKUP_GLOBAL(cl_uchar, matches + slot[k][j]);
 				/* a second load of the same line is a second L2 request, and this
 				 * kernel is bound by the L2 request rate */
 #if GPUPREAGG_ABLATE & 2
@@ -1917,23 +1977,10 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 				_Pragma("unroll")												\
 				for (int j = 0; j < 4; j++)										\
 				{																\
-					pg_##NAME##_base_t val;										\
-					if (narrow)													\
-						val = (pg_##NAME##_base_t)(nmin_##attno +				\
-							(cl_long)((flags[j] >> nshift_##attno) & nmask_##attno));	\
-					else if (reclen <= 16)										\
-					{															\
-						/* (offsets are uniform: the selects are scalar) */		\
-						cl_uint	wi = recoff_##attno >> 2;						\
-						cl_uint	lo = (wi == 1 ? words[k][j][1] : wi == 2 ? words[k][j][2] : words[k][j][3]);	\
-						cl_uint	hi = (wi == 2 ? words[k][j][3] : 0u);				\
-						cl_ulong bits = (((cl_ulong)hi << 32) | lo) >> ((recoff_##attno & 3u) * 8u);	\
-						__builtin_memcpy(&val, &bits, sizeof(val));				\
-					}															\
-					else														\
-						val = *(const pg_##NAME##_base_t *)						\
-							(recs + (size_t)reclen * slot[k][j] + recoff_##attno);	\
-					T.v_##attno[k][j] = val;									\
+					T.v_##attno[k][j] = gpupreagg_dimrec_value<pg_##NAME##_base_t>(narrow, reclen,	\
+						flags[j], words[k][j][1], words[k][j][2], words[k][j][3],	\
+						recs + (size_t)reclen * slot[k][j], recoff_##attno,		\
+						nshift_##attno, nmask_##attno, nmin_##attno);			\
 					nn |= (((flags[j] >> recbit_##attno) & 1u) ? 0u : (1u << j));	\
 				}																\
 				/* (left: the columns of a row without a partner are NULL, whatever slot 0 says) */	\
@@ -1941,6 +1988,15 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 			}
 			STROM_KVAR_LIST(X)
 #undef X
+			if (tracked)
+			{
+				/* the quad's verdicts are known: the few stores (in the chunk, a key, the slot present) */
+				const cl_uint	hit = (~(gone[k] | absent) & 0xfu);
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+					if (((hit >> j) & 1) && mflag[k][j] == 0)
+						*(__attribute__((address_space(1))) cl_uchar *)(matches + slot[k][j]) = 1;
+			}
 		}
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
@@ -1995,6 +2051,8 @@ gpupreagg_dense_lookup_body(kern_gpupreagg *kgpreagg,
 	gpupreagg_writeback_summag(kgpreagg, summag);
 }
 
+/* (a program built for the unmatched pass alone has no use for the chunk folds) */
+#if !defined(GPUPREAGG_UNMATCHED_RECLEN)
 extern "C" __global__ void
 __launch_bounds__(GPUPREAGG_BLOCK)
 gpupreagg_dense_lookup(kern_gpupreagg *kgpreagg,
@@ -2046,6 +2104,8 @@ gpupreagg_packed_lookup(kern_gpupreagg *kgpreagg,
 #endif
 }
 #endif
+
+#endif	/* !GPUPREAGG_UNMATCHED_RECLEN */
 
 /* ====================================================================== *
  * star join as lookups + dense-id reduction in ONE pass over the outer chunk
@@ -2103,6 +2163,14 @@ gpupreagg_packed_lookup(kern_gpupreagg *kgpreagg,
 #ifndef GPUPREAGG_STAR_JOINTYPE_4
 #define GPUPREAGG_STAR_JOINTYPE_4	0
 #endif
+/* the TRACKED relation (1-based; absent: none), inner or left: joined LAST, as a RIGHT or FULL join of it --
+ * its slots' matched flags are set by the rows that have a partner in it AND survive every other relation */
+#ifndef GPUPREAGG_STAR_TRACK_REL
+#define GPUPREAGG_STAR_TRACK_REL	0
+#endif
+#if GPUPREAGG_STAR_TRACK_REL < 0 || GPUPREAGG_STAR_TRACK_REL > GPUPREAGG_STAR_NRELS
+#error "GPUPREAGG_STAR_TRACK_REL: 0 .. GPUPREAGG_STAR_NRELS"
+#endif
 
 template <int KEYLEN> struct gpupreagg_star_key { typedef cl_int type; };
 template <> struct gpupreagg_star_key<8> { typedef cl_long type; };
@@ -2121,8 +2189,10 @@ template <> struct gpupreagg_star_rel<r> {												\
 	 * folded": bit absent_shift + j of the tile's gone[] words says that row j was not probed here */	\
 	static constexpr bool		keeps_absent = (jointype == 1 || jointype == 3);		\
 	static constexpr int		absent_shift = 4 * r;									\
+	static constexpr int		index = r;												\
 	static_assert(jointype >= 0 && jointype <= 3, "star join type");						\
 	static_assert(jointype < 2 || inner_mask == 0, "a semi or anti relation serves no column");	\
+	static_assert(jointype < 2 || r != GPUPREAGG_STAR_TRACK_REL, "the tracked relation joins inner or left");	\
 	static_assert(GPUPREAGG_STAR_KEYLEN_##r == 4 || GPUPREAGG_STAR_KEYLEN_##r == 8, "star key width");	\
 	static_assert(narrow ? (reclen == 2 || reclen == 4) : (reclen == 8 || reclen == 16),	\
 				  "star slot record: 2 / 4 bytes narrow, 8 or 16 bytes");					\
@@ -2237,7 +2307,12 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 	/* a qual that reads outer columns only is evaluated BEFORE any probe (see
 	 * gpupreagg_dense_lookup_body); gpupreagg_dense_row evaluates it again, errors included, for
 	 * the rows that are folded (all inner: that have a partner in every relation) */
-	const bool	qual_first = ((GPUPREAGG_QUAL_VARMASK & GPUPREAGG_STAR_INNER_ALL) == 0 && GPUPREAGG_QUAL_VARMASK != 0);
+	/* (a tracked program has none: a row the WHERE rejects still matches its slot, so every row with keys is
+	 * probed -- gpupreagg_dense_lookup_body says how the flags are read and written) */
+	constexpr int track_rel = GPUPREAGG_STAR_TRACK_REL;
+	const bool	qual_first = (track_rel == 0 && (GPUPREAGG_QUAL_VARMASK & GPUPREAGG_STAR_INNER_ALL) == 0 &&
+							  GPUPREAGG_QUAL_VARMASK != 0);
+	cl_uchar   *matches = (track_rel != 0 ? (cl_uchar *)smap->matches : (cl_uchar *)NULL);
 	/* (an inner column may be NULL whatever the chunk's bitmaps say) */
 	const cl_uint rowflags = ((any_nulls || GPUPREAGG_STAR_INNER_ALL != 0) ? 0u : ROWFLAG_ALL_NOTNULL);
 
@@ -2282,6 +2357,11 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 	};
 	/* the probes of relation P: one load per row; dead rows, and those a left or anti relation
 	 * has no slot for, at slot 0 */
+	/* the tracked relation's part of a tile: the rows' slots (the probe overwrites them), their matched flags as
+	 * they were, and which rows had no partner there -- dead code in a program without GPUPREAGG_STAR_TRACK_REL */
+	cl_uint		tslot[GPUPREAGG_QUADS][4];
+	cl_uchar	mflag[GPUPREAGG_QUADS][4];
+	cl_uint		tabsent[GPUPREAGG_QUADS];
 	auto probe = [&](auto &P, const cl_uint (&gone)[GPUPREAGG_QUADS])
 	{
 		typedef typename gpupreagg_star_unref<decltype(P)>::type::rel rel;
@@ -2294,6 +2374,12 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 			{
 				cl_uint		slot = (((masked >> j) & 1) ? 0u : P.w[k][j][0]);
 				const char *rec = P.recs + (size_t)rel::reclen * slot;
+				if (track_rel != 0 && rel::index == track_rel)
+				{
+					/* (the flag's address needs no record: its load goes out with the probe) */
+					tslot[k][j] = slot;
+					mflag[k][j] = STAR_GLOBAL(cl_uchar, matches + slot);
+				}
 				if (rel::narrow)
 					P.w[k][j][0] = (rel::reclen == 2 ? (cl_uint)STAR_GLOBAL(cl_ushort, rec) : STAR_GLOBAL(cl_uint, rec));
 				else if (rel::reclen == 8)
@@ -2408,24 +2494,12 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 			_Pragma("unroll")													\
 			for (int j = 0; j < 4; j++)											\
 			{																	\
-				pg_##NAME##_base_t val;											\
 				cl_uint	flags = P.w[k][j][0];									\
-				if (rel::narrow)												\
-					val = (pg_##NAME##_base_t)(nmin_##attno +					\
-						(cl_long)((flags >> nshift_##attno) & nmask_##attno));	\
-				else															\
-				{																\
-					/* (offsets are uniform: the selects are scalar) */			\
-					cl_uint	wi = recoff_##attno >> 2;							\
-					cl_uint	w1 = P.w[k][j][rel::nwords > 1 ? 1 : 0];			\
-					cl_uint	w2 = (rel::nwords > 2 ? P.w[k][j][rel::nwords > 2 ? 2 : 0] : 0u);	\
-					cl_uint	w3 = (rel::nwords > 3 ? P.w[k][j][rel::nwords > 3 ? 3 : 0] : 0u);	\
-					cl_uint	lo = (wi == 1 ? w1 : wi == 2 ? w2 : w3);			\
-					cl_uint	hi = (wi == 2 ? w3 : 0u);							\
-					cl_ulong bits = (((cl_ulong)hi << 32) | lo) >> ((recoff_##attno & 3u) * 8u);	\
-					__builtin_memcpy(&val, &bits, sizeof(val));					\
-				}																\
-				T.v_##attno[k][j] = val;										\
+				T.v_##attno[k][j] = gpupreagg_dimrec_value<pg_##NAME##_base_t>(rel::narrow, rel::reclen,	\
+					flags, P.w[k][j][rel::nwords > 1 ? 1 : 0],					\
+					(rel::nwords > 2 ? P.w[k][j][rel::nwords > 2 ? 2 : 0] : 0u),	\
+					(rel::nwords > 3 ? P.w[k][j][rel::nwords > 3 ? 3 : 0] : 0u),	\
+					(const char *)NULL, recoff_##attno, nshift_##attno, nmask_##attno, nmin_##attno);	\
 				nn |= (((flags >> recbit_##attno) & 1u) ? 0u : (1u << j));		\
 			}																	\
 			/* (left: the columns of a row without a partner are NULL, whatever slot 0 says) */	\
@@ -2444,6 +2518,8 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 				/* the record's presence bit joins the key's verdict; then the join type's select */
 				const cl_uint absent = (rel::keeps_absent ? (((gone[k] >> rel::absent_shift) & 0xfu) | ab) : ab);
 				gone[k] |= (rel::jointype == 1 ? 0u : rel::jointype == 3 ? (~absent & 0xfu) : ab);
+				if (track_rel != 0 && rel::index == track_rel)
+					tabsent[k] = absent;
 				STROM_KVAR_LIST(X)
 			}
 		};
@@ -2451,6 +2527,21 @@ gpupreagg_star_lookup_body(kern_gpupreagg *kgpreagg,
 #define M(r)	decode(P##r);
 		GPUPREAGG_STAR_REL_LIST(M)
 #undef M
+		if (track_rel != 0)
+		{
+			/* the last relation is decoded, so every verdict is in: a row matches its slot of the tracked
+			 * relation when it is folded as far as the join goes (in the chunk, kept by every other relation)
+			 * and had a partner there.  The few stores. */
+#pragma unroll
+			for (int k = 0; k < GPUPREAGG_QUADS; k++)
+			{
+				const cl_uint	hit = (~(gone[k] | tabsent[k]) & 0xfu);
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+					if (((hit >> j) & 1) && mflag[k][j] == 0)
+						*(__attribute__((address_space(1))) cl_uchar *)(matches + tslot[k][j]) = 1;
+			}
+		}
 #pragma unroll
 		for (int k = 0; k < GPUPREAGG_QUADS; k++)
 		{
@@ -2519,6 +2610,151 @@ gpupreagg_packed_lookup_star(kern_gpupreagg *kgpreagg,
 #endif
 #undef STAR_GLOBAL
 #endif	/* GPUPREAGG_STAR_NRELS */
+
+/* ====================================================================== *
+ * the unmatched pass of a tracked lookup or star (RIGHT / FULL joins)
+ *
+ * After the last chunk: one row per slot of the tracked relation that is present and whose matched
+ * flag is still 0.  The row is NULL-extended -- the columns the tracked relation serves come from the
+ * slot record, with the record's own NULL bits, every other variable of the program (fact columns,
+ * text ones included, other relations' columns) is NULL -- and goes through the program's qual and
+ * into the fold like any row: gpupreagg_dense_row, the LDS image, slab and merge of
+ * gpupreagg_dense_lookup, with the same control block.  No chunk is read.
+ *
+ * The kernel exists only in a program built for the tracked relation's record facts
+ * (GPUPREAGG_UNMATCHED_RECLEN / _NARROW / _INNER_MASK; gpupreagg.cpp: unmatched_mapping_defines): it
+ * depends on no fact column's width and no key width.  Slots are walked in tiles of
+ * GPUPREAGG_TILE_ROWS, four consecutive slots a thread: records and flag bytes stream, coalesced.
+ * jmap->unmatched_wgs caps the work-groups of a role that walk (STROM_GPUPREAGG_UNMATCHED_MAX_GRID);
+ * the merge adds up every slab, so the others still store their empty one.  Dense accumulators
+ * only: packed ones sum fact columns, which are all NULL here.
+ * ====================================================================== */
+#if defined(GPUPREAGG_UNMATCHED_RECLEN)
+#if !defined(GPUPREAGG_UNMATCHED_NARROW) || !defined(GPUPREAGG_UNMATCHED_INNER_MASK)
+#error "GPUPREAGG_UNMATCHED_RECLEN comes with GPUPREAGG_UNMATCHED_NARROW and GPUPREAGG_UNMATCHED_INNER_MASK"
+#endif
+extern "C" __global__ void
+__launch_bounds__(GPUPREAGG_BLOCK)
+gpupreagg_dense_lookup_unmatched(kern_gpupreagg *kgpreagg,
+								 const gpupreagg_joined_map *jmap,
+								 const gpupreagg_dense_ctl *ctl_in_memory,
+								 char *slabs)
+{
+	extern __shared__ __attribute__((aligned(16))) char lds[];
+	/* the control block by value (see gpupreagg_dense_column) */
+	const gpupreagg_dense_ctl ctl_by_value = *ctl_in_memory;
+	const gpupreagg_dense_ctl *ctl = &ctl_by_value;
+	const kern_parambuf *kparams = KERN_GPUPREAGG_PARAMBUF(kgpreagg);
+	constexpr cl_uint reclen = GPUPREAGG_UNMATCHED_RECLEN;
+	constexpr bool	narrow = (GPUPREAGG_UNMATCHED_NARROW != 0);
+	static_assert(narrow ? (reclen == 2 || reclen == 4) : (reclen >= 8 && reclen % 4 == 0), "slot record");
+	cl_uint		nslots = strom_uniform((cl_uint)jmap->nslots);
+	cl_uint		ntiles = (nslots + GPUPREAGG_TILE_ROWS - 1) / GPUPREAGG_TILE_ROWS;
+	cl_uint		nsplits = ctl->nsplits;
+	cl_uint		G = ctl->groups_per_split;
+	cl_uint		NREP = ctl->nrep;
+	cl_uint		split = blockIdx.x % nsplits;
+	cl_uint		wg_in_split = blockIdx.x / nsplits;
+	cl_uint		wgs_per_split = gridDim.x / nsplits;
+	cl_uint		walkers = strom_uniform((cl_uint)jmap->unmatched_wgs);
+	cl_uint		gid_lo = split * G;
+	cl_uint		rep = threadIdx.x & (NREP - 1);
+	cl_int		chunk_status = StromError_Success;
+	cl_ulong	summag = 0;
+	cl_int		param_error = StromError_Success;
+	strom_kparams KP;
+	gpupreagg_lds_layout L;
+
+	gpupreagg_load_kparams(KP, kparams, &param_error);
+	gpupreagg_remap_init(ctl);
+	gpupreagg_lds_layout_init(L, G, NREP);
+	gpupreagg_lds_init(lds, L, G, NREP);
+	if (walkers == 0 || walkers > wgs_per_split)
+		walkers = wgs_per_split;
+#define X(attno,colidx,NAME)													\
+	constexpr bool	inner_##attno = ((((GPUPREAGG_UNMATCHED_INNER_MASK) >> (colidx)) & 1UL) != 0);	\
+	const cl_uint recoff_##attno = strom_uniform((cl_uint)jmap->c[colidx].dimvalues);	\
+	const cl_uint recbit_##attno = strom_uniform((cl_uint)jmap->c[colidx].dimisnull);	\
+	const cl_uint nshift_##attno = strom_uniform((cl_uint)jmap->nshift[colidx]);	\
+	const cl_uint nmask_##attno = strom_uniform((cl_uint)jmap->nmask[colidx]);	\
+	const cl_long nmin_##attno = strom_uniform((cl_long)jmap->nmin[colidx]);
+	STROM_KVAR_LIST(X)
+#undef X
+	const char *recs = (const char *)jmap->recs;
+	const cl_uchar *matches = (const cl_uchar *)jmap->matches;
+	char	   *my_slab = slabs + (size_t)blockIdx.x * ctl->slab_bytes;
+#define UNMATCHED_GLOBAL(T, p)	(*(const __attribute__((address_space(1))) T *)(p))
+
+	for (cl_uint tile = wg_in_split; wg_in_split < walkers && tile < ntiles; tile += walkers)
+	{
+		cl_uint		tile_base = tile * GPUPREAGG_TILE_ROWS;
+		cl_uint		words[GPUPREAGG_QUADS][4][4];
+		cl_uchar	mflag[GPUPREAGG_QUADS][4];
+
+		/* every load of the tile before the first is used; a slot past the table reads slot 0 */
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+			cl_uint	slot0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				cl_uint		slot = (slot0 + j < nslots ? slot0 + j : 0u);
+				const char *rec = recs + (size_t)reclen * slot;
+				mflag[k][j] = UNMATCHED_GLOBAL(cl_uchar, matches + slot);
+				words[k][j][1] = words[k][j][2] = words[k][j][3] = 0;
+				if (narrow)
+					words[k][j][0] = (reclen == 2 ? (cl_uint)UNMATCHED_GLOBAL(cl_ushort, rec) : UNMATCHED_GLOBAL(cl_uint, rec));
+				else if (reclen == 8)
+				{
+					cl_ulong w = UNMATCHED_GLOBAL(cl_ulong, rec);
+					words[k][j][0] = (cl_uint)w;
+					words[k][j][1] = (cl_uint)(w >> 32);
+				}
+				else if (reclen == 16)
+				{
+					strom_quad<cl_uint>::vec_t q = UNMATCHED_GLOBAL(strom_quad<cl_uint>::vec_t, rec);
+					words[k][j][0] = q.x; words[k][j][1] = q.y; words[k][j][2] = q.z; words[k][j][3] = q.w;
+				}
+				else
+					words[k][j][0] = UNMATCHED_GLOBAL(cl_uint, rec);
+			}
+		}
+#pragma unroll
+		for (int k = 0; k < GPUPREAGG_QUADS; k++)
+		{
+			cl_uint	slot0 = tile_base + (k * GPUPREAGG_BLOCK + threadIdx.x) * 4;
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+			{
+				/* a row: the slot exists, holds a dimension row, and no fact row matched it */
+				if (!(slot0 + j < nslots && (words[k][j][0] & 1u) != 0 && mflag[k][j] == 0))
+					continue;
+				strom_kvars	KV;
+#define X(attno,colidx,NAME)													\
+				if (inner_##attno)													\
+					KV.KVAR_##attno = pg_##NAME##_make(								\
+						gpupreagg_dimrec_value<pg_##NAME##_base_t>(narrow, reclen,		\
+							words[k][j][0], words[k][j][1], words[k][j][2], words[k][j][3],	\
+							recs + (size_t)reclen * (slot0 + j), recoff_##attno,		\
+							nshift_##attno, nmask_##attno, nmin_##attno),				\
+						((words[k][j][0] >> recbit_##attno) & 1u) != 0);				\
+				else																\
+					KV.KVAR_##attno = pg_##NAME##_make((pg_##NAME##_base_t)0, true);
+				STROM_KVAR_LIST(X)
+#undef X
+				STROM_KVARS_FINISH(KV);
+				gpupreagg_dense_row(lds, ctl, L, KP, KV, gid_lo, G, NREP, rep,
+									param_error, &chunk_status, summag, 0u);
+			}
+		}
+	}
+#undef UNMATCHED_GLOBAL
+	gpupreagg_store_slab(lds, L, my_slab, G, NREP, &chunk_status, 0u);
+	gpupreagg_writeback_status(&kgpreagg->status, chunk_status);
+	gpupreagg_writeback_summag(kgpreagg, summag);
+}
+#endif	/* GPUPREAGG_UNMATCHED_RECLEN */
 
 /* ====================================================================== *
  * register accumulators: at most GPUPREAGG_REG_GROUPS dense ids

@@ -62,6 +62,8 @@ struct strom_hashjoin_table {
 		dimrec_narrow		narrow;
 	};
 	std::map<std::string, composed_dimrecs> composed;
+	/* entries with a NULL key, counted on first use (hashjoin_table_null_key_entries); -1: not yet */
+	long				null_key_entries = -1;
 };
 
 extern "C" strom_hashjoin_table *
@@ -1795,6 +1797,44 @@ strom::hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min,
 	/* a WHERE pulled up into the join program: only the join kernels evaluate it */
 	if (p_has_outer_qual)
 		*p_has_outer_qual = (strstr(tbl->prog->source.c_str(), "#define HASHJOIN_FAST_OUTER_QUAL 1") != nullptr);
+	return 0;
+}
+
+/*
+ * For the tracked lookup folds (gpupreagg.cpp): the table's identity for the life of the process, and how many
+ * of its entries have a NULL key.  Such an entry has no slot (hashjoin_build_index_kernel leaves it out of the
+ * probe index), so a pass over the SLOTS can never emit it.  The index head counts every entry, NULL keys
+ * included, and nothing counts the occupied slots: they are counted here, once per table -- the 4-byte slot
+ * array comes to the host in pieces -- and with unique keys every occupied slot is one entry.
+ */
+int
+strom::hashjoin_table_null_key_entries(strom_hashjoin_table *tbl, uint64_t *p_serial, cl_uint *p_count)
+{
+	if (!tbl || tbl->ntables != 1 || tbl->head.rel[0].mode != HASHJOIN_MODE_DIRECT || !tbl->head.rel[0].unique)
+		return StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(tbl->dim_lock);
+	if (tbl->null_key_entries < 0)
+	{
+		const hashjoin_index_rel &ir = tbl->head.rel[0];
+		const size_t	piece = (size_t)1 << 20;			/* slots a copy */
+		std::vector<cl_uint> buf(std::min<size_t>(piece, ir.nslots));
+		size_t		occupied = 0;
+		(void)hipSetDevice(tbl->dev->hip_id);
+		for (size_t at = 0; at < ir.nslots; at += piece)
+		{
+			size_t	n = std::min<size_t>(piece, ir.nslots - at);
+			if (hipMemcpy(buf.data(), tbl->d_index + ir.slots_off + sizeof(cl_uint) * at, sizeof(cl_uint) * n,
+						  hipMemcpyDeviceToHost) != hipSuccess)
+				return StromError_HipInternal;
+			for (size_t i = 0; i < n; i++)
+				occupied += (buf[i] != 0);
+		}
+		if (occupied > ir.nentries)
+			return StromError_DataStoreCorruption;
+		tbl->null_key_entries = (long)(ir.nentries - occupied);
+	}
+	*p_serial = tbl->serial;
+	*p_count = (cl_uint)tbl->null_key_entries;
 	return 0;
 }
 

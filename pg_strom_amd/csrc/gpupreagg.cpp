@@ -106,6 +106,18 @@ struct strom_gpupreagg {
 	/* the session's source built behind a define block -- FOR a column mapping (lookup_mapping_program,
 	 * star_mapping_program), with GPUPREAGG_CHECKED (checked_program) -- by that block */
 	std::map<std::string, std::pair<strom_devprog_key, Program *>> lookup_programs;	/* (program_with_defines) */
+	/*
+	 * the matched flags of the TRACKED relation of this session's lookup folds (RIGHT / FULL joins:
+	 * strom_submit_gpupreagg_lookup_tracked): one byte per slot of that table, 0 unmatched, 1 matched.  The
+	 * slot records belong to the table and are shared between sessions; what matched is a fact of one query,
+	 * so the flags are the session's -- made (zeroed) by its first tracked request or its unmatched call,
+	 * bound to (table, tracked position, slots) from then on, freed with the session.  (under 'lock')
+	 */
+	char			   *d_matches = nullptr;
+	size_t				matches_len = 0;			/* == the table's nslots */
+	uint64_t			matches_serial = 0;			/* the table (hashjoin_table_null_key_entries) */
+	int					matches_pos = 0;			/* the tracked relation, 1-based */
+	bool				unmatched_done = false;		/* the unmatched pass ran: no fold, no second pass before a reset */
 	char			   *d_export_spec = nullptr;	/* preagg_export_spec of this table (fetch on the device) */
 	/* the program's text / character(n) variables: { attno, type oid } (its STROM_KVARLENA_LIST) */
 	std::vector<std::pair<int, int>> varlena_vars;
@@ -509,6 +521,7 @@ enum preagg_kind {
 	PREAGG_JOINED,			/* a finished GpuHashJoin's result pairs (strom_submit_gpupreagg_joined) */
 	PREAGG_LOOKUP,			/* the chunk's rows, the join a lookup in the aggregate's pass (..._lookup) */
 	PREAGG_STAR,			/* ... a lookup in every relation of a star (..._lookup_star) */
+	PREAGG_UNMATCHED,		/* no chunk: the unmatched slots of a tracked relation (..._lookup_unmatched) */
 };
 
 struct preagg_request {
@@ -526,7 +539,7 @@ struct preagg_request {
 	/* the program to fold with when it is not the session's own: the one built for this column
 	 * mapping (lookup, star), or the checked one of a retry (checked_program) */
 	Program			   *prog = nullptr;
-	/* joined, lookup: a gpupreagg_joined_map; star: a gpupreagg_star_map (write_joined_map / write_star_map) */
+	/* joined, lookup, unmatched: a gpupreagg_joined_map; star: a gpupreagg_star_map (write_joined_map / write_star_map) */
 	std::shared_ptr<std::vector<char>> map;
 	/* the define block 'prog' was built with, for checked_program to build again behind GPUPREAGG_CHECKED: a star's,
 	 * and a TYPED one-table lookup's.  EMPTY for an inner one-table lookup, on purpose: its checked retry folds with
@@ -658,6 +671,11 @@ struct fold_mapping {
 	cl_ulong	recs[GPUPREAGG_STAR_MAXRELS];			/* device address of the slot records */
 	/* how the relation's presence enters the fold: 0 inner, 1 left, 2 semi, 3 anti (..._lookup_typed) */
 	int32_t		jointype[GPUPREAGG_STAR_MAXRELS] = {};
+	/* the tracked relation (1-based, 0: none) and the session's matched flags of its table (..._lookup_tracked);
+	 * the unmatched pass: the work-groups of a role that walk the slots (0: all) */
+	int			tracked = 0;
+	cl_ulong	matches = 0;
+	cl_uint		unmatched_wgs = 0;
 };
 
 /*
@@ -669,10 +687,11 @@ struct fold_mapping {
 /* the define block of a one-table mapping (strom_gpupreagg.h: GPUPREAGG_LOOKUP_*); an inner join names
  * no join type, so its block -- and its program -- is the one it always was.  "" = no valid mapping */
 std::string
-lookup_mapping_defines(int keylen, int reclen, int narrow, uint64_t inner_mask, int jointype)
+lookup_mapping_defines(int keylen, int reclen, int narrow, uint64_t inner_mask, int jointype, bool track = false)
 {
 	bool	ok = (narrow ? (reclen == 2 || reclen == 4) : (reclen >= 8 && reclen % 4 == 0));
-	if (!ok || !(keylen == 4 || keylen == 8) || jointype < 0 || jointype > 3 || (jointype >= 2 && inner_mask != 0))
+	if (!ok || !(keylen == 4 || keylen == 8) || jointype < 0 || jointype > 3 || (jointype >= 2 && inner_mask != 0) ||
+		(track && jointype >= 2))				/* (a tracked relation joins inner or left: RIGHT, FULL) */
 		return "";
 	char		defs[512];
 	int			n = snprintf(defs, sizeof(defs),
@@ -681,22 +700,27 @@ lookup_mapping_defines(int keylen, int reclen, int narrow, uint64_t inner_mask, 
 			 "#define GPUPREAGG_LOOKUP_KEYLEN %d\n",
 			 (unsigned long)inner_mask, (unsigned)reclen, narrow ? 1u : 0u, keylen);
 	if (jointype != 0)
-		snprintf(defs + n, sizeof(defs) - n, "#define GPUPREAGG_LOOKUP_JOINTYPE %d\n", jointype);
+		n += snprintf(defs + n, sizeof(defs) - n, "#define GPUPREAGG_LOOKUP_JOINTYPE %d\n", jointype);
+	if (track)
+		snprintf(defs + n, sizeof(defs) - n, "#define GPUPREAGG_LOOKUP_TRACK 1\n");
 	return defs;
 }
 
 Program *
 lookup_mapping_program(strom_gpupreagg *sess, const fold_mapping &m, std::string *p_typed_defs, int *p_errcode)
 {
-	/* the run-time form: any INNER mapping, no build (it knows no join type: a typed lookup is always built) */
-	if (m.jointype[0] == 0 && getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
+	/* the run-time form: any INNER mapping, no build (it knows no join type and no flags: a typed or tracked
+	 * lookup is always built) */
+	const bool	plain = (m.jointype[0] == 0 && m.tracked == 0);
+	if (plain && getenv("STROM_GPUPREAGG_LOOKUP_GENERIC"))
 		return nullptr;
 	/* (the checks of lookup_mapping_defines hold for every mapping build_fold_mapping describes: keys of 4 or 8
 	 * bytes, narrow records of 2 or 4, plain ones of 8, 16, 32 or a multiple of 64 -- hashjoin_table_dimrecs.  An
 	 * inner mapping that failed them would fold by the run-time form, which reads any mapping; a typed one has no
 	 * other kernel and is refused) */
-	std::string	defs = lookup_mapping_defines(m.key_attlen[0], m.reclen[0], m.narrow[0], m.inner_mask[0], m.jointype[0]);
-	if (m.jointype[0] == 0)
+	std::string	defs = lookup_mapping_defines(m.key_attlen[0], m.reclen[0], m.narrow[0], m.inner_mask[0], m.jointype[0],
+											  m.tracked != 0);
+	if (plain)
 		return (defs.empty() ? nullptr : program_with_defines(sess, defs));
 	if (defs.empty())
 	{
@@ -713,9 +737,10 @@ lookup_mapping_program(strom_gpupreagg *sess, const fold_mapping &m, std::string
 /* the define block of a star mapping (strom_gpupreagg.h: GPUPREAGG_STAR_*); "" = no valid mapping */
 std::string
 star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, const int32_t *narrow,
-					 const uint64_t *inner_mask, const int32_t *jointype = nullptr)
+					 const uint64_t *inner_mask, const int32_t *jointype = nullptr, int tracked = 0)
 {
-	if (nrels < 1 || nrels > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask)
+	if (nrels < 1 || nrels > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask ||
+		tracked < 0 || tracked > nrels || (tracked != 0 && jointype && jointype[tracked - 1] >= 2))
 		return "";
 	char		buf[256];
 	snprintf(buf, sizeof(buf), "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_STAR_NRELS %d\n", nrels);
@@ -747,6 +772,27 @@ star_mapping_defines(int nrels, const int32_t *keylen, const int32_t *reclen, co
 	}
 	if (total > GPUPREAGG_STAR_MAXRECBYTES)
 		return "";
+	if (tracked != 0)
+	{
+		snprintf(buf, sizeof(buf), "#define GPUPREAGG_STAR_TRACK_REL %d\n", tracked);
+		defs += buf;
+	}
+	return defs;
+}
+
+/* the define block of the unmatched pass (strom_gpupreagg.h: gpupreagg_dense_lookup_unmatched): the tracked
+ * relation's record facts and nothing else -- no fact column's width, no key width, so one program serves the
+ * one-table call and every star around that relation.  "" = no valid records */
+std::string
+unmatched_mapping_defines(int reclen, int narrow, uint64_t inner_mask)
+{
+	if (!(narrow ? (reclen == 2 || reclen == 4) : (reclen >= 8 && reclen % 4 == 0)))
+		return "";
+	char		defs[384];
+	snprintf(defs, sizeof(defs),
+			 "#define GPUPREAGG_LOOKUP_ONLY 1\n#define GPUPREAGG_UNMATCHED_RECLEN %u\n"
+			 "#define GPUPREAGG_UNMATCHED_NARROW %u\n#define GPUPREAGG_UNMATCHED_INNER_MASK 0x%lxUL\n",
+			 (unsigned)reclen, narrow ? 1u : 0u, (unsigned long)inner_mask);
 	return defs;
 }
 
@@ -770,7 +816,8 @@ checked_program(const preagg_request &req)
 {
 	/* (a typed one-table lookup brings its block too: the run-time form of the kernel knows no join type) */
 	return program_with_defines(req.sess, "#define GPUPREAGG_CHECKED 1\n" +
-								((req.kind == PREAGG_STAR || req.kind == PREAGG_LOOKUP) ? req.mapping_defs : std::string()));
+								((req.kind == PREAGG_STAR || req.kind == PREAGG_LOOKUP || req.kind == PREAGG_UNMATCHED)
+								 ? req.mapping_defs : std::string()));
 }
 
 /*
@@ -864,6 +911,7 @@ const char *const fold_kernels[][2] = {
 	/* PREAGG_JOINED */	{ "gpupreagg_dense_joined", nullptr },
 	/* PREAGG_LOOKUP */	{ "gpupreagg_dense_lookup", "gpupreagg_packed_lookup" },
 	/* PREAGG_STAR */	{ "gpupreagg_dense_lookup_star", "gpupreagg_packed_lookup_star" },
+	/* PREAGG_UNMATCHED */	{ "gpupreagg_dense_lookup_unmatched", nullptr },
 };
 
 /*
@@ -925,7 +973,8 @@ int
 plan_fold(Device *dev, Program *prog, const preagg_request &req, bool checked, fold_plan *plan)
 {
 	strom_gpupreagg *sess = req.sess;
-	bool		use_lookup = (req.kind == PREAGG_LOOKUP || req.kind == PREAGG_STAR);
+	/* (the unmatched pass walks slots in the lookups' tiles; it reads no chunk: no column directory) */
+	bool		use_lookup = (req.kind == PREAGG_LOOKUP || req.kind == PREAGG_STAR || req.kind == PREAGG_UNMATCHED);
 	int			errcode = 0;
 	const char *name = fold_kernels[req.kind][0], *name_packed = fold_kernels[req.kind][1];
 
@@ -1035,7 +1084,9 @@ send_request(strom_task_impl *task, const preagg_request &req, hipStream_t s_in,
 				 "send kern_gpupreagg", false);
 	task->pfm.num_dma_send++;
 	task->pfm.bytes_dma_send += send_len;
-	if (req.kds_dev)
+	if (req.kind == PREAGG_UNMATCHED)
+		out->d_kds = nullptr;						/* (no chunk) */
+	else if (req.kds_dev)
 		out->d_kds = req.kds_dev->devptr;
 	else
 	{
@@ -1129,13 +1180,14 @@ queue_fold_and_merge(strom_task_impl *task, const preagg_request &req, Program *
 	const void *a_jmap = d_jmap;
 	const void *a_pack = sent.d_kg + sent.kg_len;
 	/* the fold kernels' parameters, every kind's in this one order: kg, [result pairs,] kds,
-	 * [toast, row map,] [column mapping,] ctl, [pack ctl,] slabs */
+	 * [toast, row map,] [column mapping,] ctl, [pack ctl,] slabs; the unmatched pass has no kds */
 	void	   *fold_args[8];
 	int			na = 0;
 	fold_args[na++] = &a_kg;
 	if (req.kind == PREAGG_JOINED)
 		fold_args[na++] = &a_res;
-	fold_args[na++] = &a_kds;
+	if (req.kind != PREAGG_UNMATCHED)
+		fold_args[na++] = &a_kds;
 	if (req.kind == PREAGG_PLAIN && !plan.use_column)
 	{
 		fold_args[na++] = &a_toast;
@@ -2543,16 +2595,21 @@ collect_relation_columns(int depth, int ncols, const int32_t *src_depth, const i
  * slot records made and describes the result in *m.  Returns 0, or the code to refuse the request with.
  * The entry points answer some faults with different codes and in a different order; callers may rely on
  * either, so each difference is kept and marked where the code branches on the entry: (1) to (4) below.
+ * PREAGG_UNMATCHED (strom_submit_gpupreagg_lookup_unmatched) describes the mapping of a lookup (ntbls == 1) or
+ * a star WITHOUT a chunk: outer is NULL, so nothing is held against a chunk's head -- no key width, no fact
+ * column's width, no text variable's column (every fact column of that pass is NULL) -- and only relation
+ * 'tracked' has its slot records made, the same records the folds of that mapping read.
  */
 int
 build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jtask,
 				   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
 				   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
-				   fold_mapping *m)
+				   fold_mapping *m, int tracked = 0)
 {
-	const bool	star = (entry == PREAGG_STAR);
+	const bool	nochunk = (entry == PREAGG_UNMATCHED);
+	const bool	star = (entry == PREAGG_STAR || (nochunk && ntbls != 1));
 
-	if (!sess || sess->hashed || !sess->has_domain || (entry == PREAGG_JOINED && !jtask) || !tbls || !outer ||
+	if (!sess || sess->hashed || !sess->has_domain || (entry == PREAGG_JOINED && !jtask) || !tbls || (!outer) != nochunk ||
 		ntbls < 1 || ntbls > GPUPREAGG_STAR_MAXRELS ||
 		ncols < 1 || ncols > GPUPREAGG_JOINED_MAXCOLS || !src_depth || !src_colidx || !type_oids)
 		return StromError_BadRequestMessage;
@@ -2563,13 +2620,13 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 		task_wait_completed(jtask);
 	/* needs: (joined) a finished join with STROM_RESULTS_ON_DEVICE; per table one inner relation with a DIRECT
 	 * index and unique keys, joined on a plain outer column; a resident COLUMN chunk; all on the session's device */
-	int			outer_ncols = (int)outer->head.ncols;
+	int			outer_ncols = (nochunk ? 0 : (int)outer->head.ncols);
 	bool		ok = (!jtask || (jtask->res_is_join && jtask->keep_main && jtask->errcode == 0 && jtask->main_devptr));
 	/* the records of the unmatched pass of a RIGHT / FULL join have no outer row (word 0 == 0): the
 	 * joined fold reads the outer chunk at word 0 - 1 and would leave it.  They go through
 	 * strom_hashjoin_project_column(task, tbl, NULL, ..) and a plain fold. */
 	ok = ok && !(jtask && jtask->res_is_unmatched);
-	ok = ok && outer->head.format == KDS_FORMAT_COLUMN && outer->dindex == sess->dev->dindex;
+	ok = ok && (nochunk || (outer->head.format == KDS_FORMAT_COLUMN && outer->dindex == sess->dev->dindex));
 	m->ncols = ncols;
 	m->nrels = ntbls;
 	for (int r = 0; ok && r < ntbls; r++)
@@ -2584,7 +2641,7 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 			   * matches (RIGHT / FULL) would keep every flag clear and its unmatched pass would
 			   * silently emit matched entries.  The joined fold is fine: the join ran and flagged. */
 			  !(entry != PREAGG_JOINED && strom_hashjoin_table_tracked_depth(tbls[r]) != 0) &&
-			  key_attno >= 1 && key_attno <= outer_ncols && tbl_dindex == sess->dev->dindex);
+			  key_attno >= 1 && (nochunk || key_attno <= outer_ncols) && tbl_dindex == sess->dev->dindex);
 		m->key_col[r] = key_attno - 1;
 	}
 	if (!ok)
@@ -2598,16 +2655,16 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 	(void)hipSetDevice(sess->dev->hip_id);
 	/* the outer chunk's column widths */
 	std::vector<char> ohead(KDS_HEAD_LENGTH(outer_ncols));
-	if (hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
+	if (!nochunk && hipMemcpy(ohead.data(), outer->devptr, ohead.size(), hipMemcpyDeviceToHost) != hipSuccess)
 		return StromError_BadRequestMessage;
 	const kern_data_store *oh = (const kern_data_store *)ohead.data();
 	/* (these kernels stream the outer columns: a text variable must be one of them) */
-	if (!varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
+	if (!nochunk && !varlena_mapping_ok(sess, ncols, src_depth, src_colidx, type_oids, oh))
 		return StromError_BadRequestMessage;
 	/* (2) the width of a join key: 4 or 8 bytes for a lookup (BadRequest), 1, 2, 4 or 8 for result
 	 * pairs (DataStoreCorruption); the star looks BEFORE the columns, the one-table calls AFTER */
 	auto key_widths = [&]() -> int {
-		for (int r = 0; r < ntbls; r++)
+		for (int r = 0; r < ntbls && !nochunk; r++)
 		{
 			int		len = m->key_attlen[r] = oh->colmeta[m->key_col[r]].attlen;
 			if (!(len == 4 || len == 8 || (entry == PREAGG_JOINED && (len == 1 || len == 2))))
@@ -2630,7 +2687,8 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 			 * a negative oid it takes text for an 8-byte value, and refuses */
 			int		oid = (star ? type_oids[i] : type_oids[i] < 0 ? -type_oids[i] : type_oids[i]);
 			int		attlen = ((oid == STROM_TEXTOID || oid == STROM_BPCHARNOID) ? -1 : type_length(oid));
-			if (src_colidx[i] < 0 || src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen)
+			if (!nochunk &&
+				(src_colidx[i] < 0 || src_colidx[i] >= outer_ncols || oh->colmeta[src_colidx[i]].attlen != attlen))
 				return StromError_DataStoreCorruption;
 		}
 		else if (src_depth[i] < 1 || src_depth[i] > ntbls || src_colidx[i] < 0)
@@ -2641,6 +2699,11 @@ build_fold_mapping(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jt
 		return rc;
 	for (int r = 0; r < ntbls; r++)
 	{
+		m->inner_mask[r] = 0;
+		m->reclen[r] = m->narrow[r] = 0;
+		m->recs[r] = 0;
+		if (nochunk && r + 1 != tracked)
+			continue;
 		/* one packed record per slot: presence, NULL bits and the wanted columns of relation r + 1 */
 		int			cols[HASHJOIN_DIMREC_MAXCOLS], lens[HASHJOIN_DIMREC_MAXCOLS];
 		int			which[HASHJOIN_DIMREC_MAXCOLS], ints[HASHJOIN_DIMREC_MAXCOLS];
@@ -2824,6 +2887,8 @@ write_joined_map(const fold_mapping &m)
 	jm->recs = m.recs[0];
 	jm->reclen = m.reclen[0];
 	jm->narrow = m.narrow[0];
+	jm->matches = m.matches;
+	jm->unmatched_wgs = m.unmatched_wgs;
 	for (int i = 0; i < m.ncols; i++)
 	{
 		jm->c[i].depth = m.c[i].depth;
@@ -2856,6 +2921,7 @@ write_star_map(const fold_mapping &m)
 		sm->rel[r].narrow = m.narrow[r];
 	}
 	memcpy(sm->c, m.c, sizeof(sm->c[0]) * m.ncols);
+	sm->matches = m.matches;
 	return img;
 }
 
@@ -2876,13 +2942,32 @@ launch_fused_fold(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jta
 	req.sess = sess;
 	req.kds_dev = outer;
 	req.format = KDS_FORMAT_COLUMN;
-	req.nrows = outer->head.nitems;
+	req.nrows = (outer ? outer->head.nitems : 0);
 	req.kind = entry;
-	if (entry == PREAGG_STAR)
+	if (entry == PREAGG_UNMATCHED)
+	{
+		/* (m is the one-relation mapping of the tracked relation: its slots are the rows) */
+		req.mapping_defs = unmatched_mapping_defines(m.reclen[0], m.narrow[0], m.inner_mask[0]);
+		if (req.mapping_defs.empty())
+		{
+			*p_errcode = StromError_BadRequestMessage;
+			return nullptr;
+		}
+		req.prog = program_with_defines(sess, req.mapping_defs);
+		if (!req.prog)
+		{
+			*p_errcode = StromError_OutOfMemory;
+			return nullptr;
+		}
+		req.map = write_joined_map(m);
+		req.nrows = m.nslots[0];
+	}
+	else if (entry == PREAGG_STAR)
 	{
 		/* (a record longer than GPUPREAGG_STAR_MAXRECLEN, or more than GPUPREAGG_STAR_MAXRECBYTES over
 		 * all relations: no define block -- the kernel keeps a row's records in registers) */
-		req.mapping_defs = star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask, m.jointype);
+		req.mapping_defs = star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask, m.jointype,
+												m.tracked);
 		if (req.mapping_defs.empty())
 		{
 			*p_errcode = StromError_BadRequestMessage;
@@ -2924,12 +3009,62 @@ launch_fused_fold(strom_gpupreagg *sess, preagg_kind entry, strom_task_impl *jta
 	return task;
 }
 
+/*
+ * The session's matched flags for tracked relation 'pos' of a fold over 'tbl' (nslots slots): made on first
+ * use, zeroed, and from then on bound to that table and position.  A table with a NULL-key entry is refused:
+ * such an entry has no slot, the unmatched pass could never emit it, and the caller takes the join's RIGHT
+ * path, which does.  for_fold: a chunk fold, which may not follow the unmatched pass without a reset; the
+ * unmatched pass itself may not run twice.  Returns 0 and the flags' address, or the code to refuse with.
+ */
+static int
+session_bind_matches(strom_gpupreagg *sess, strom_hashjoin_table *tbl, int pos, cl_uint nslots, bool for_fold,
+					 cl_ulong *p_matches)
+{
+	uint64_t	serial = 0;
+	cl_uint		null_keys = 0;
+	int			rc = hashjoin_table_null_key_entries(tbl, &serial, &null_keys);
+	if (rc != 0)
+		return rc;
+	if (null_keys != 0)
+		return StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(sess->lock);
+	if (sess->d_matches)
+	{
+		if (sess->matches_serial != serial || sess->matches_pos != pos || sess->matches_len != nslots ||
+			sess->unmatched_done)
+			return StromError_BadRequestMessage;
+	}
+	else
+	{
+		Device *dev = sess->dev;
+		(void)hipSetDevice(dev->hip_id);
+		char   *p = (char *)dev->pool.alloc(nslots);
+		if (!p)
+			return StromError_OutOfMemory;
+		if (hipMemset(p, 0, nslots) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+		{
+			dev->pool.release(p);
+			return StromError_HipInternal;
+		}
+		sess->d_matches = p;
+		sess->matches_len = nslots;
+		sess->matches_serial = serial;
+		sess->matches_pos = pos;
+		sess->unmatched_done = false;
+	}
+	if (!for_fold)
+		sess->unmatched_done = true;
+	*p_matches = (cl_ulong)(uintptr_t)sess->d_matches;
+	return 0;
+}
+
 /* _joined, _lookup and _lookup_star: build_fold_mapping, then the launch */
 static strom_task *
 submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *join_handle,
 					   strom_hashjoin_table *const *tbls, int ntbls, strom_dstore *outer,
 					   int ncols, const int32_t *src_depth, const int32_t *src_colidx, const int32_t *type_oids,
-					   strom_done_cb done, void *arg, int *p_errcode, const int32_t *jointypes = nullptr)
+					   strom_done_cb done, void *arg, int *p_errcode, const int32_t *jointypes = nullptr,
+					   int tracked = 0)
 {
 	STROM_ABI_TRY
 	int		dummy;
@@ -2942,6 +3077,18 @@ submit_gpupreagg_fused(strom_gpupreagg *sess, preagg_kind entry, strom_task *joi
 		return nullptr;
 	for (int r = 0; jointypes && r < ntbls; r++)
 		m.jointype[r] = jointypes[r];
+	if (tracked != 0)
+	{
+		/* (a star's records must fit the kernel whatever is tracked: refuse before the flags are made) */
+		if (entry == PREAGG_STAR &&
+			star_mapping_defines(m.nrels, m.key_attlen, m.reclen, m.narrow, m.inner_mask, m.jointype, tracked).empty())
+			*p_errcode = StromError_BadRequestMessage;
+		else
+			*p_errcode = session_bind_matches(sess, tbls[tracked - 1], tracked, m.nslots[tracked - 1], true, &m.matches);
+		if (*p_errcode != 0)
+			return nullptr;
+		m.tracked = tracked;
+	}
 	return launch_fused_fold(sess, entry, jtask, m, outer, done, arg, p_errcode);
 	STROM_ABI_CATCH(nullptr, p_errcode)
 }
@@ -3058,6 +3205,194 @@ strom_submit_gpupreagg_lookup_typed(strom_gpupreagg *sess,
 	}
 	return submit_gpupreagg_fused(sess, ntbls == 1 ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
 								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode, jointypes);
+}
+
+/* the checks of the tracked calls on top of the typed call's: join types 0 .. 3, no column under a semi or anti
+ * relation, tracked 1 .. ntbls and that relation inner or left */
+static bool
+tracked_arguments_ok(int ntbls, const int32_t *jointypes, int tracked, int ncols, const int32_t *src_depth)
+{
+	bool	ok = (jointypes && ntbls >= 1 && ntbls <= GPUPREAGG_STAR_MAXRELS && tracked >= 1 && tracked <= ntbls);
+	for (int r = 0; ok && r < ntbls; r++)
+		ok = (jointypes[r] >= 0 && jointypes[r] <= 3);
+	ok = ok && jointypes[tracked - 1] <= 1;
+	for (int i = 0; ok && src_depth && i < ncols && i < GPUPREAGG_JOINED_MAXCOLS; i++)
+		ok = !(src_depth[i] >= 1 && src_depth[i] <= ntbls && jointypes[src_depth[i] - 1] >= 2);
+	return ok;
+}
+
+extern "C" int
+strom_gpupreagg_lookup_tracked_defines(int ntbls, const int32_t *keylen, const int32_t *reclen,
+									   const int32_t *narrow, const uint64_t *inner_mask, const int32_t *jointypes,
+									   int tracked, char *buf, size_t buflen)
+{
+	if (tracked == 0)
+		return strom_gpupreagg_lookup_typed_defines(ntbls, keylen, reclen, narrow, inner_mask, jointypes, buf, buflen);
+	if (ntbls < 1 || ntbls > GPUPREAGG_STAR_MAXRELS || !keylen || !reclen || !narrow || !inner_mask || !jointypes ||
+		tracked < 1 || tracked > ntbls)
+		return -1;
+	std::string	defs = (ntbls == 1 ? lookup_mapping_defines(keylen[0], reclen[0], narrow[0], inner_mask[0], jointypes[0], true)
+						   : star_mapping_defines(ntbls, keylen, reclen, narrow, inner_mask, jointypes, tracked));
+	if (defs.empty() || !buf || defs.size() + 1 > buflen)
+		return -1;
+	memcpy(buf, defs.c_str(), defs.size() + 1);
+	return (int)defs.size();
+}
+
+extern "C" int
+strom_gpupreagg_lookup_unmatched_defines(int reclen, int narrow, uint64_t inner_mask, char *buf, size_t buflen)
+{
+	std::string	defs = unmatched_mapping_defines(reclen, narrow, inner_mask);
+	if (defs.empty() || !buf || defs.size() + 1 > buflen)
+		return -1;
+	memcpy(buf, defs.c_str(), defs.size() + 1);
+	return (int)defs.size();
+}
+
+extern "C" strom_task *
+strom_submit_gpupreagg_lookup_tracked(strom_gpupreagg *sess,
+									  strom_hashjoin_table *const *tbls, int ntbls, const int32_t *jointypes,
+									  int tracked, strom_dstore *outer,
+									  int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+									  const int32_t *type_oids,
+									  strom_done_cb done, void *arg, int *p_errcode)
+{
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	/* (nothing tracked: the typed call -- its code path, its error codes, its programs) */
+	if (tracked == 0)
+		return strom_submit_gpupreagg_lookup_typed(sess, tbls, ntbls, jointypes, outer, ncols, src_depth, src_colidx,
+												   type_oids, done, arg, p_errcode);
+	if (!tracked_arguments_ok(ntbls, jointypes, tracked, ncols, src_depth))
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	return submit_gpupreagg_fused(sess, ntbls == 1 ? PREAGG_LOOKUP : PREAGG_STAR, nullptr, tbls, ntbls, outer,
+								  ncols, src_depth, src_colidx, type_oids, done, arg, p_errcode, jointypes, tracked);
+}
+
+extern "C" strom_task *
+strom_submit_gpupreagg_lookup_unmatched(strom_gpupreagg *sess,
+										strom_hashjoin_table *const *tbls, int ntbls, const int32_t *jointypes,
+										int tracked,
+										int ncols, const int32_t *src_depth, const int32_t *src_colidx,
+										const int32_t *type_oids,
+										strom_done_cb done, void *arg, int *p_errcode)
+{
+	STROM_ABI_TRY
+	int		dummy;
+	if (!p_errcode)
+		p_errcode = &dummy;
+	if (!tracked_arguments_ok(ntbls, jointypes, tracked, ncols, src_depth))
+	{
+		*p_errcode = StromError_BadRequestMessage;
+		return nullptr;
+	}
+	fold_mapping m;
+	*p_errcode = build_fold_mapping(sess, PREAGG_UNMATCHED, nullptr, tbls, ntbls, nullptr, ncols, src_depth, src_colidx,
+									type_oids, &m, tracked);
+	if (*p_errcode != 0)
+		return nullptr;
+	/* the tracked relation alone, as a one-relation mapping: its records, its columns; every other column
+	 * keeps depth and col for the record, and is NULL in the kernel */
+	const int	t = tracked - 1;
+	fold_mapping u = m;
+	u.nrels = 1;
+	u.key_col[0] = m.key_col[t];
+	u.key_attlen[0] = 0;
+	u.reclen[0] = m.reclen[t];
+	u.narrow[0] = m.narrow[t];
+	u.inner_mask[0] = m.inner_mask[t];
+	u.key_min[0] = m.key_min[t];
+	u.nslots[0] = m.nslots[t];
+	u.recs[0] = m.recs[t];
+	u.tracked = tracked;
+	*p_errcode = session_bind_matches(sess, tbls[t], tracked, u.nslots[0], false, &u.matches);
+	if (*p_errcode != 0)
+		return nullptr;
+	/* every fold of this table queued so far has set its flags before the pass reads them */
+	(void)hipSetDevice(sess->dev->hip_id);
+	if (hipDeviceSynchronize() != hipSuccess)
+	{
+		*p_errcode = StromError_HipInternal;
+		return nullptr;
+	}
+	/* a cap on the work-groups that walk the slots (tests: one work-group walks many tiles); read on every call */
+	if (const char *v = getenv("STROM_GPUPREAGG_UNMATCHED_MAX_GRID"))
+		u.unmatched_wgs = (cl_uint)std::max(1, atoi(v) / (int)std::max<cl_uint>(1, sess->ctl.nsplits));
+	return launch_fused_fold(sess, PREAGG_UNMATCHED, nullptr, u, nullptr, done, arg, p_errcode);
+	STROM_ABI_CATCH(nullptr, p_errcode)
+}
+
+/* the flags of the session's tracked relation: the multi-GPU / multi-shard seam, and the reset of a rescan.
+ * Each synchronises the device first (strom_hip.h). */
+extern "C" size_t
+strom_gpupreagg_lookup_matches_length(strom_gpupreagg *sess)
+{
+	if (!sess)
+		return 0;
+	std::lock_guard<std::mutex> g(sess->lock);
+	return (sess->d_matches ? sess->matches_len : 0);
+}
+
+extern "C" int
+strom_gpupreagg_lookup_matches_fetch(strom_gpupreagg *sess, void *buf, size_t len)
+{
+	if (!sess || !buf)
+		return StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(sess->lock);
+	if (!sess->d_matches || len != sess->matches_len)
+		return StromError_BadRequestMessage;
+	(void)hipSetDevice(sess->dev->hip_id);
+	if (hipDeviceSynchronize() != hipSuccess ||
+		hipMemcpy(buf, sess->d_matches, len, hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_HipInternal;
+	return 0;
+}
+
+extern "C" int
+strom_gpupreagg_lookup_matches_merge(strom_gpupreagg *sess, const void *buf, size_t len)
+{
+	STROM_ABI_TRY
+	if (!sess || !buf)
+		return StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(sess->lock);
+	if (!sess->d_matches || len != sess->matches_len)
+		return StromError_BadRequestMessage;
+	const unsigned char *in = (const unsigned char *)buf;
+	for (size_t i = 0; i < len; i++)
+		if (in[i] > 1)
+			return StromError_BadRequestMessage;		/* (no image of these flags: nothing is merged) */
+	std::vector<unsigned char> mine(len);
+	(void)hipSetDevice(sess->dev->hip_id);
+	if (hipDeviceSynchronize() != hipSuccess ||
+		hipMemcpy(mine.data(), sess->d_matches, len, hipMemcpyDeviceToHost) != hipSuccess)
+		return StromError_HipInternal;
+	for (size_t i = 0; i < len; i++)
+		mine[i] |= in[i];
+	if (hipMemcpy(sess->d_matches, mine.data(), len, hipMemcpyHostToDevice) != hipSuccess)
+		return StromError_HipInternal;
+	return 0;
+	STROM_ABI_CATCH(StromError_OutOfMemory, (int *)nullptr)
+}
+
+extern "C" int
+strom_gpupreagg_lookup_reset_matches(strom_gpupreagg *sess)
+{
+	if (!sess)
+		return StromError_BadRequestMessage;
+	std::lock_guard<std::mutex> g(sess->lock);
+	if (!sess->d_matches)
+		return StromError_BadRequestMessage;
+	(void)hipSetDevice(sess->dev->hip_id);
+	if (hipDeviceSynchronize() != hipSuccess ||
+		hipMemset(sess->d_matches, 0, sess->matches_len) != hipSuccess ||
+		hipDeviceSynchronize() != hipSuccess)
+		return StromError_HipInternal;
+	sess->unmatched_done = false;
+	return 0;
 }
 
 extern "C" int
@@ -3669,6 +4004,8 @@ strom_gpupreagg_release(strom_gpupreagg *sess)
 		dev->pool.release(sess->d_remap);
 	if (sess->d_export_spec)
 		dev->pool.release(sess->d_export_spec);
+	if (sess->d_matches)
+		dev->pool.release(sess->d_matches);
 	for (auto &kv : sess->packed)
 	{
 		dev->pool.release(kv.second.d_ctl);

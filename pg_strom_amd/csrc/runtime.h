@@ -285,6 +285,9 @@ int			hashjoin_snowflake_dimrecs(strom_hashjoin_table *const *tbls, int ntbls, c
 									   void **p_recs, unsigned *p_reclen, dimrec_narrow *narrow);
 int			hashjoin_table_direct_info(strom_hashjoin_table *tbl, cl_long *p_key_min, cl_uint *p_nslots,
 									   int *p_outer_key_attno, int *p_dindex, int *p_has_outer_qual = nullptr);
+/* the table's serial number (its identity: an address is used again) and the number of its entries with a NULL
+ * key, which have no slot; one relation, DIRECT index, unique keys (BadRequest otherwise).  Blocks on first use. */
+int			hashjoin_table_null_key_entries(strom_hashjoin_table *tbl, uint64_t *p_serial, cl_uint *p_count);
 /* textdict.cpp, for the table that keeps a coded column (gpuhashjoin.cpp: strom_textdict_encode_table).
  * A dictionary is known to its tables by (serial, epoch): the serial is its own for the life of the
  * process, the epoch counts its resets; a released dictionary has no current epoch at all. */

@@ -128,6 +128,40 @@ def lookup_typed_defines(relations, jointypes):
     return buf.value.decode()
 
 
+def lookup_tracked_defines(relations, jointypes, tracked):
+    """lookup_typed_defines for a mapping with a TRACKED relation (strom_gpupreagg_lookup_tracked_defines):
+    tracked is 0 .. len(relations), 1-based; 0 gives lookup_typed_defines' text byte for byte, otherwise
+    the block ends in one more line, GPUPREAGG_LOOKUP_TRACK 1 (one relation) or GPUPREAGG_STAR_TRACK_REL d.
+    ValueError: what lookup_typed_defines refuses, tracked out of range or naming a semi / anti relation."""
+    n = len(relations)
+    jts = _jointype_codes(jointypes)
+    if len(jts) != n:
+        raise ValueError("one join type per relation")
+    keylen = np.array([r[0] for r in relations], dtype=np.int32)
+    reclen = np.array([r[1] for r in relations], dtype=np.int32)
+    narrow = np.array([1 if r[2] else 0 for r in relations], dtype=np.int32)
+    masks = np.array([sum(1 << c for c in r[3]) for r in relations], dtype=np.uint64)
+    buf = ctypes.create_string_buffer(4096)
+    rc = lib.strom_gpupreagg_lookup_tracked_defines(n, keylen.ctypes.data, reclen.ctypes.data,
+                                                    narrow.ctypes.data, masks.ctypes.data, jts.ctypes.data,
+                                                    int(tracked), buf, len(buf))
+    if rc < 0:
+        raise ValueError("no tracked lookup mapping: %r, %r, tracked %r" % (relations, list(jointypes), tracked))
+    return buf.value.decode()
+
+
+def lookup_unmatched_defines(relation):
+    """the define block of the unmatched pass over a tracked relation (gpupreagg_dense_lookup_unmatched;
+    strom_gpupreagg_lookup_unmatched_defines): relation as in lookup_star_defines -- only its record length,
+    form and served columns count, the key length is ignored."""
+    buf = ctypes.create_string_buffer(1024)
+    rc = lib.strom_gpupreagg_lookup_unmatched_defines(int(relation[1]), 1 if relation[2] else 0,
+                                                      sum(1 << c for c in relation[3]), buf, len(buf))
+    if rc < 0:
+        raise ValueError("no slot records: %r" % (relation,))
+    return buf.value.decode()
+
+
 def lookup_snowflake_roots(parents, column_depths):
     """which star a snowflake flattens to (strom_gpupreagg_lookup_snowflake_roots; no device needed):
     parents[d - 1] is 0 for a relation joined on a fact column, p < d for one joined on a column of
@@ -361,6 +395,75 @@ class GpuPreAgg(object):
         if not task:
             raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_typed")
         return (task, chunk, (depth, colidx, oids, tbls, jts))
+
+    def submit_lookup_tracked(self, joins, jointypes, tracked, chunk, columns):
+        """submit_lookup_typed with ONE tracked relation (strom_submit_gpupreagg_lookup_tracked): relation
+        'tracked' (1-based; 0: none, which is submit_lookup_typed) is joined LAST, as a RIGHT join when its
+        join type is "inner" and a FULL join when it is "left" -- (fact JOIN the others) RIGHT|FULL JOIN
+        tracked.  The chunk is folded exactly as submit_lookup_typed folds it; on the side the kernel
+        flags the slots of the tracked table that had a partner, in an area this session owns.  After the
+        last chunk submit_lookup_unmatched folds the slots without one."""
+        depth, colidx, oids = _column_mapping(columns)
+        jts = _jointype_codes(jointypes)
+        if len(jts) != len(joins):
+            raise ValueError("one join type per relation")
+        tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpupreagg_lookup_tracked(self.session, tbls, len(joins),
+                                                         jts.ctypes.data if len(jts) else None, int(tracked),
+                                                         chunk.handle,
+                                                         len(columns), depth.ctypes.data, colidx.ctypes.data,
+                                                         oids.ctypes.data, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_tracked")
+        return (task, chunk, (depth, colidx, oids, tbls, jts))
+
+    def submit_lookup_unmatched(self, joins, jointypes, tracked, columns):
+        """the unmatched pass of the same mapping (strom_submit_gpupreagg_lookup_unmatched), after the folds
+        of every chunk have been collected: one NULL-extended row per present slot of the tracked table
+        that no fact row matched -- its own columns from the slot record, every other variable NULL --
+        through the qual and into this session.  Reads no chunk; collect() the result.  Once per scan:
+        reset_lookup_matches() re-arms it."""
+        depth, colidx, oids = _column_mapping(columns)
+        jts = _jointype_codes(jointypes)
+        if len(jts) != len(joins):
+            raise ValueError("one join type per relation")
+        tbls = (ctypes.c_void_p * max(1, len(joins)))(*[j.table for j in joins])
+        err = ctypes.c_int(0)
+        task = lib.strom_submit_gpupreagg_lookup_unmatched(self.session, tbls, len(joins),
+                                                           jts.ctypes.data if len(jts) else None, int(tracked),
+                                                           len(columns), depth.ctypes.data, colidx.ctypes.data,
+                                                           oids.ctypes.data, None, None, ctypes.byref(err))
+        if not task:
+            raise runtime.StromError(err.value, "strom_submit_gpupreagg_lookup_unmatched")
+        return (task, None, (depth, colidx, oids, tbls, jts))
+
+    def lookup_matches(self):
+        """the matched flags of the tracked table, one uint8 per slot (0 unmatched, 1 matched): the
+        multi-GPU / multi-shard seam (strom_gpupreagg_lookup_matches_fetch)"""
+        n = lib.strom_gpupreagg_lookup_matches_length(self.session)
+        if n == 0:
+            raise runtime.StromError(101, "strom_gpupreagg_lookup_matches_length: no tracked relation")
+        img = np.zeros(n, dtype=np.uint8)
+        rc = lib.strom_gpupreagg_lookup_matches_fetch(self.session, img.ctypes.data, n)
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_gpupreagg_lookup_matches_fetch")
+        return img
+
+    def merge_lookup_matches(self, image):
+        """OR another session's (rank's, shard's) flag image into this one's
+        (strom_gpupreagg_lookup_matches_merge): same length, bytes 0 / 1, BadRequest and nothing merged otherwise"""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        rc = lib.strom_gpupreagg_lookup_matches_merge(self.session, img.ctypes.data, len(img))
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_gpupreagg_lookup_matches_merge")
+
+    def reset_lookup_matches(self):
+        """every slot unmatched again and the unmatched pass re-armed, for a rescan
+        (strom_gpupreagg_lookup_reset_matches)"""
+        rc = lib.strom_gpupreagg_lookup_reset_matches(self.session)
+        if rc != 0:
+            raise runtime.StromError(rc, "strom_gpupreagg_lookup_reset_matches")
 
     def mapping_defines(self):
         """the define blocks of the programs this session has built for fused folds so far

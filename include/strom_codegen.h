@@ -116,6 +116,20 @@ int		strom_codegen_gpuhashjoin(const char *spec, strom_codegen_result *out, int 
  */
 int		strom_codegen_available_expression(const char *expr, char **errmsg);
 
+/*
+ * The device function catalog, read only (devfunc_common_catalog, codegen.c:211-630): entry
+ * 'index' of 0 .. strom_codegen_catalog_count() - 1 in catalog order.  *p_name points at the
+ * library's own copy of the pg_proc name (do not free), argtypes[0 .. nargs-1] receive the
+ * argument STROM_*OIDs (at most STROM_CATALOG_MAX_ARGS), *p_rettype the result's, *p_flags the
+ * DEVFUNC_NEEDS_* of the declaring library.  Returns the number of arguments, -1 when index is
+ * out of range, -2 for an entry with more than STROM_CATALOG_MAX_ARGS arguments (nothing is
+ * written then).  Any out pointer may be NULL.
+ */
+#define STROM_CATALOG_MAX_ARGS	4
+int		strom_codegen_catalog_count(void);
+int		strom_codegen_catalog_entry(int index, const char **p_name, int32_t *argtypes,
+									int32_t *p_rettype, int32_t *p_flags);
+
 void	strom_codegen_release(strom_codegen_result *res);
 
 /*

@@ -1408,7 +1408,13 @@ eval_func(const oracle_expr *e, oracle_value *a, int32_t *errcode)
 				else if (t0 == STROM_BOOLOID)
 					c = ((a[0].v.i != 0) > (a[1].v.i != 0)) - ((a[0].v.i != 0) < (a[1].v.i != 0));
 				else if (t0 == STROM_BPCHAROID)
-					c = ((uint8_t)a[0].v.i > (uint8_t)a[1].v.i) - ((uint8_t)a[0].v.i < (uint8_t)a[1].v.i);
+				{
+					/* a blank is padding: the empty string, below every character
+					 * (bpchar_truelen, opencl_textlib.h:154-167); else bytewise, unsigned */
+					int l = ((uint8_t)a[0].v.i == ' ' ? -1 : (int)(uint8_t)a[0].v.i);
+					int rr = ((uint8_t)a[1].v.i == ' ' ? -1 : (int)(uint8_t)a[1].v.i);
+					c = (l > rr) - (l < rr);
+				}
 				else
 					c = (a[0].v.i > a[1].v.i) - (a[0].v.i < a[1].v.i);
 				switch (e->op)
@@ -1542,8 +1548,23 @@ eval_func(const oracle_expr *e, oracle_value *a, int32_t *errcode)
 		case OP_ATAN2: r.v.d = atan2(a[0].v.d, a[1].v.d); return r;
 		case OP_DATE_PLI: case OP_DATE_MII: case OP_INT_PL_DATE: case OP_DATE_MI:
 			{
-				__int128 x = a[0].v.i, y = a[1].v.i, z, lo, hi;
+				/* x is the date (integer_pl_date: its second argument), y what is added */
+				int		swap = (e->op == OP_INT_PL_DATE);
+				__int128 x = a[swap].v.i, y = a[!swap].v.i, z, lo, hi;
+				int		x_inf = (x == INT32_MIN || x == INT32_MAX);
 				int_range(STROM_INT4OID, &lo, &hi);
+				if (e->op == OP_DATE_MI)
+				{
+					/* an infinite operand: back to the CPU (opencl_timelib.h:368) */
+					if (x_inf || y == INT32_MIN || y == INT32_MAX)
+						return recheck(rt, errcode);
+				}
+				else if (x_inf)
+				{
+					/* "can't change infinity" (opencl_timelib.h:335, 353) */
+					r.v.i = (int64_t)x;
+					return r;
+				}
 				z = (e->op == OP_DATE_MII || e->op == OP_DATE_MI) ? x - y : x + y;
 				if (z < lo || z > hi)
 					return recheck(rt, errcode);
@@ -1556,22 +1577,22 @@ eval_func(const oracle_expr *e, oracle_value *a, int32_t *errcode)
 			else if (__builtin_mul_overflow(a[0].v.i, (int64_t)86400000000LL, &r.v.i))
 				return recheck(rt, errcode);
 			return r;
-		case OP_TS_TO_DATE:
-			if (a[0].v.i == INT64_MIN) { r.v.i = INT32_MIN; return r; }
-			if (a[0].v.i == INT64_MAX) { r.v.i = INT32_MAX; return r; }
+		case OP_TS_TO_DATE: case OP_TS_TO_TIME:
+			if (a[0].v.i == INT64_MIN || a[0].v.i == INT64_MAX)
 			{
-				int64_t t = a[0].v.i, d = t / 86400000000LL;
-				if (t % 86400000000LL < 0) d--;
-				r.v.i = d;
+				if (e->op == OP_TS_TO_TIME)
+					return make_null(rt);
+				r.v.i = (a[0].v.i == INT64_MIN ? INT32_MIN : INT32_MAX);
 				return r;
 			}
-		case OP_TS_TO_TIME:
-			if (a[0].v.i == INT64_MIN || a[0].v.i == INT64_MAX)
-				return make_null(rt);
 			{
-				int64_t t = a[0].v.i % 86400000000LL;
-				if (t < 0) t += 86400000000LL;
-				r.v.i = t;
+				int64_t d = a[0].v.i / 86400000000LL, t = a[0].v.i % 86400000000LL;
+				if (t < 0) { t += 86400000000LL; d--; }
+				/* timestamp2tm refuses a negative Julian day (opencl_timelib.h:204-209; 246, 271).
+				 * Its upper bound, INT_MAX, is out of reach of int64 microseconds. */
+				if (d + 2451545 < 0)
+					return recheck(rt, errcode);
+				r.v.i = (e->op == OP_TS_TO_DATE ? d : t);
 				return r;
 			}
 		case OP_NUM_ADD: case OP_NUM_SUB:

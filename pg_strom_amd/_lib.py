@@ -267,6 +267,9 @@ PROTOTYPES = {
                                           ctypes.POINTER(c_int)]),
     "strom_codegen_available_expression": (c_int, [c_char_p, ctypes.POINTER(c_void_p)]),
     "strom_codegen_release": (None, [ctypes.POINTER(strom_codegen_result)]),
+    "strom_codegen_catalog_count": (c_int, []),
+    "strom_codegen_catalog_entry": (c_int, [c_int, ctypes.POINTER(c_char_p), ctypes.POINTER(c_int32),
+                                            ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)]),
     "strom_create_kern_parambuf": (c_void_p, [ctypes.POINTER(strom_codegen_result),
                                               ctypes.POINTER(c_uint64),
                                               ctypes.POINTER(ctypes.c_uint8), c_int]),

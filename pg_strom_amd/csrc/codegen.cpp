@@ -274,7 +274,8 @@ build_catalog(void)
 		add_func("bpcharcmp", {CN,CN}, I4, "bpcharcmp", S);
 		add_func("bttextcmp", {TX,TX}, I4, "text_cmp", S);
 	}
-	/* bpchar(1) by value: bytewise comparison (textlib's role for Q1 keys) */
+	/* bpchar(1) by value: bpchar_compare on one byte -- a blank is the empty string, other bytes
+	 * compare unsigned (textlib's role for Q1 keys) */
 	for (const char *op : {"eq","ne","lt","le","gt","ge"})
 		add_func(std::string("bpchar") + op, {C1,C1}, B, std::string("char1") + op, M);
 	add_func("bpcharcmp", {C1,C1}, I4, "char1cmp", M);
@@ -1256,6 +1257,35 @@ strom_codegen_available_expression(const char *expr, char **errmsg)
 			*errmsg = strdup(e.what());
 		return 0;
 	}
+}
+
+extern "C" int
+strom_codegen_catalog_count(void)
+{
+	if (devfunc_catalog.empty())
+		build_catalog();
+	return (int)devfunc_catalog.size();
+}
+
+extern "C" int
+strom_codegen_catalog_entry(int index, const char **p_name, int32_t *argtypes,
+							int32_t *p_rettype, int32_t *p_flags)
+{
+	if (index < 0 || index >= strom_codegen_catalog_count())
+		return -1;
+	const devfunc_info &f = devfunc_catalog[index];
+	int		nargs = (int)f.argtypes.size();
+	if (nargs > STROM_CATALOG_MAX_ARGS)
+		return -2;		/* raise STROM_CATALOG_MAX_ARGS with the first such function */
+	if (p_name)
+		*p_name = f.name.c_str();
+	for (int i = 0; argtypes && i < nargs; i++)
+		argtypes[i] = f.argtypes[i];
+	if (p_rettype)
+		*p_rettype = f.rettype;
+	if (p_flags)
+		*p_flags = f.flags;
+	return nargs;
 }
 
 extern "C" void

@@ -1395,22 +1395,73 @@ hash_table_head(const strom_gpupreagg *sess, cl_uint capacity, size_t *p_total)
 	return head;
 }
 
+/* launch step A -- the STROM_GPUPREAGG_HASH_* knobs (README), read on every call: tests change the
+ * environment between two folds of one process.  A value that fails its reader's test is ignored. */
+struct hashed_knobs {
+	cl_uint		lds_slots, roles, parts, unit_rows, scatter_rows;		/* 0: not set */
+	unsigned	scatter_block, fold_block;								/* 0: not set */
+	unsigned	check_block, check_per_cu, unit_lds_kb;
+	cl_ulong	parts_min;
+	cl_ulong	fill_num, fill_den;	/* the part of a role's LDS table its share of the groups may fill */
+	bool		lds_64kb, no_rolemap, no_parts, no_lds_scatter, no_exact;
+};
+
+/* a power of two within lo ... hi (a work-group size: 256, 512 or 1024), or dflt */
+cl_uint
+knob_pow2(const char *name, int lo, int hi, cl_uint dflt)
+{
+	const char *v = getenv(name);
+	int		want = (v ? atoi(v) : 0);
+	return (want >= lo && want <= hi && (want & (want - 1)) == 0) ? (cl_uint)want : dflt;
+}
+/* an integer, raised to 'lo' where it is below; dflt when the knob is not set */
+int
+knob_at_least(const char *name, int lo, int dflt)
+{
+	const char *v = getenv(name);
+	return v ? std::max(lo, atoi(v)) : dflt;
+}
+
+hashed_knobs
+read_hashed_knobs()
+{
+	hashed_knobs k;
+	const char *kb = getenv("STROM_GPUPREAGG_HASH_LDS_KB"), *fill = getenv("STROM_GPUPREAGG_HASH_FILL");
+	const char *parts_min = getenv("STROM_GPUPREAGG_HASH_PARTS_MIN");
+	/* tests: a tiny table in front of the global one sends (nearly) every row to the global
+	 * table's claim / probe protocol */
+	k.lds_slots = knob_pow2("STROM_GPUPREAGG_HASH_LDS_SLOTS", 64, 16384, 0);
+	k.lds_64kb = (kb && atol(kb) <= 64);
+	k.unit_lds_kb = (cl_uint)std::min(159, knob_at_least("STROM_GPUPREAGG_HASH_UNIT_LDS_KB", 8, 159));
+	k.roles = knob_pow2("STROM_GPUPREAGG_HASH_ROLES", 1, 64, 0);	/* 1, 2, 4 ... 64; anything else would break the tile walk */
+	k.fill_num = (fill ? (cl_ulong)atoi(fill) : 5);		/* 64 probes find room at 5/8 */
+	k.fill_den = (fill ? 100 : 8);
+	k.no_rolemap = (getenv("STROM_GPUPREAGG_HASH_NO_ROLEMAP") != nullptr);
+	k.parts_min = (parts_min ? strtoul(parts_min, nullptr, 10) : 10000);
+	k.no_parts = (getenv("STROM_GPUPREAGG_HASH_NO_PARTS") != nullptr);
+	k.parts = knob_pow2("STROM_GPUPREAGG_HASH_PARTS", 64, 4096, 0);
+	k.unit_rows = (cl_uint)knob_at_least("STROM_GPUPREAGG_HASH_UNIT_ROWS", 1024, 0);
+	/* (1024 threads, two work-groups per CU: 2.37 against 2.48 ms for the whole plan with 256 x 4,
+	 * the other combinations in between -- scripts/hashed_check_sweep.sh) */
+	k.check_block = knob_pow2("STROM_GPUPREAGG_HASH_CHECK_BLOCK", 256, 1024, 1024);
+	k.check_per_cu = (unsigned)knob_at_least("STROM_GPUPREAGG_HASH_CHECK_PER_CU", 1, 2);
+	k.scatter_block = knob_pow2("STROM_GPUPREAGG_HASH_SCATTER_BLOCK", 256, 1024, 0);
+	k.fold_block = knob_pow2("STROM_GPUPREAGG_HASH_FOLD_BLOCK", 256, 1024, 0);
+	k.no_lds_scatter = (getenv("STROM_GPUPREAGG_HASH_NO_LDS_SCATTER") != nullptr);
+	k.scatter_rows = (cl_uint)knob_at_least("STROM_GPUPREAGG_HASH_SCATTER_ROWS", 1, 0);
+	k.no_exact = (getenv("STROM_GPUPREAGG_HASH_NO_EXACT") != nullptr);
+	return k;
+}
+
 /* slots of the work-group's LDS table in front of the global one, and its bytes */
 cl_uint
-hash_lds_slots(const strom_gpupreagg *sess, size_t *p_bytes, bool for_units = false)
+hash_lds_slots(const strom_gpupreagg *sess, const hashed_knobs &knobs, size_t *p_bytes, bool for_units = false)
 {
 	size_t		nkeys = sess->key_resno.size();
 	/* after the table: GPUPREAGG_HASH_QUEUE queued row numbers per wave (used with roles) */
 	size_t		queue = (for_units ? 16 /* the unit's flags */ : ((size_t)sess->block / 64) * GPUPREAGG_HASH_QUEUE * sizeof(cl_uint));
-	auto fit = [&](size_t budget, size_t *p_b) -> cl_uint {
-		cl_uint	slots = 16384;
-		for (;;)
-		{
-			*p_b = sess->image_offset(sess->nsections(), slots, 1) + (size_t)slots * GPUPREAGG_HASH_LDS_ENTRY(nkeys) + queue;
-			if (*p_b <= budget || slots == 64)
-				return slots;
-			slots >>= 1;
-		}
+	auto bytes_of = [&](cl_uint slots) -> size_t {
+		return sess->image_offset(sess->nsections(), slots, 1) + (size_t)slots * GPUPREAGG_HASH_LDS_ENTRY(nkeys) + queue;
 	};
 	/*
 	 * LDS per work-group: ONE work-group per CU with a table of up to 136 KB, four times the
@@ -1419,35 +1470,18 @@ hash_lds_slots(const strom_gpupreagg *sess, size_t *p_bytes, bool for_units = fa
 	 * 3.4 ms per 1e8 rows, 3e4 groups 13.2 -> 7.1 ms; a fuller small table also probes longer,
 	 * so the big one wins from 100 groups on (698 -> 656 us; 600 groups 1463 -> 932 us).
 	 * profiles/r02_hashed_lds_tables.txt
+	 * The partition plan's units: no role queues, and as much of the CU's 160 KB as a power of
+	 * two of slots takes.
 	 */
-	if (for_units)
-	{
-		/* the partition plan's units: no role queues, and as much of the CU's 160 KB as a
-		 * power of two of slots takes */
-		size_t	unit_budget = 159 * 1024;
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_UNIT_LDS_KB"))
-			unit_budget = (size_t)std::max(8L, std::min(159L, atol(v))) * 1024;
-		return fit(unit_budget, p_bytes);
-	}
-	if (const char *v = getenv("STROM_GPUPREAGG_HASH_LDS_SLOTS"))
-	{
-		/* tests: a tiny table in front of the global one sends (nearly) every row to the
-		 * global table's claim / probe protocol */
-		cl_uint		want = (cl_uint)atoi(v);
-		if (want >= 64 && want <= 16384 && (want & (want - 1)) == 0)
-		{
-			*p_bytes = sess->image_offset(sess->nsections(), want, 1) + (size_t)want * GPUPREAGG_HASH_LDS_ENTRY(nkeys) + queue;
-			return want;
-		}
-	}
-	size_t		small_bytes, big_bytes;
-	cl_uint		small_slots = fit(64 * 1024, &small_bytes);
-	cl_uint		big_slots = fit(136 * 1024, &big_bytes);
-	bool		big = true;
-	if (const char *v = getenv("STROM_GPUPREAGG_HASH_LDS_KB"))
-		big = (atol(v) > 64);
-	*p_bytes = (big ? big_bytes : small_bytes);
-	return (big ? big_slots : small_slots);
+	size_t		budget = (size_t)(for_units ? knobs.unit_lds_kb : knobs.lds_64kb ? 64 : 136) * 1024;
+	cl_uint		slots = 16384;
+	if (!for_units && knobs.lds_slots)
+		slots = knobs.lds_slots;			/* (as asked for, whatever it takes) */
+	else
+		while (bytes_of(slots) > budget && slots > 64)
+			slots >>= 1;
+	*p_bytes = bytes_of(slots);
+	return slots;
 }
 
 /* a zeroed, initialised table of 'capacity' slots on the session's stream */
@@ -1659,13 +1693,405 @@ gpupreagg_hashed_exact_merge(strom_task_impl *task, preagg_request req)
 	task_enqueue(task);
 }
 
+/* launch step B -- how this request is folded: by hash roles or by the partition plan, and every kernel's
+ * geometry.  Host arithmetic and get_function only.  The roles' LDS table and the units' have their own fields. */
+struct hashed_plan {
+	/* plan_role_table: the roles' kernels and their table; 'block' is the session's work-group size */
+	hipFunction_t fn_check = nullptr, fn_fold = nullptr;
+	unsigned	block = 0, role_fold_grid = 0;
+	cl_uint		role_lds_slots = 0;
+	size_t		role_lds_bytes = 0;
+	/* free slots a fold needs (see plan_role_table).  From the ROLES' figures for both plans: the
+	 * partition plan's turns keep this headroom too, not one made of the units' grid and table */
+	cl_ulong	headroom = 0;
+	/* plan_hashed_fold */
+	bool		column_streams = false, use_parts = false;
+	/* ... the partition plan: check, part_plan, scatter (lds_rows 0: the direct one), fold of the units */
+	hipFunction_t fn_pcheck = nullptr, fn_plan = nullptr, fn_scatter = nullptr, fn_units = nullptr;
+	cl_uint		nparts = 0, max_units = 0, lds_rows = 0, unit_lds_slots = 0;
+	size_t		reclen = 0, scatter_lds_bytes = 0, unit_lds_bytes = 0;
+	gpupreagg_part_ctl ctl_img = {};
+	unsigned	check_block = 0, check_grid = 0, scatter_block = 0, scatter_grid = 0, unit_fold_grid = 0, unit_fold_block = 0;
+};
+
+/*
+ * geometry of the roles' fold: two work-groups per CU (64 KB of LDS each), or one with the large
+ * table.  Slots can be claimed past the fill limit by threads that raced through the limit test
+ * (one each at most) and by the work-groups' final LDS flushes: that much headroom, and an
+ * eighth of the table on top, always stays free.
+ */
+int
+plan_role_table(Device *dev, Program *prog, strom_gpupreagg *sess, const hashed_knobs &knobs, hashed_plan *plan)
+{
+	int		errcode = 0;
+	plan->fn_check = prog->get_function(dev, "gpupreagg_hash_check", &errcode);
+	plan->fn_fold = plan->fn_check ? prog->get_function(dev, "gpupreagg_hash_fold", &errcode) : nullptr;
+	if (!plan->fn_check || !plan->fn_fold)
+		return errcode;
+	plan->block = (unsigned)sess->block;
+	plan->role_lds_slots = hash_lds_slots(sess, knobs, &plan->role_lds_bytes);
+	plan->role_fold_grid = (unsigned)dev->prop.multiProcessorCount * (plan->role_lds_bytes <= 72 * 1024 ? 2 : 1);
+	plan->headroom = (cl_ulong)plan->role_fold_grid * plan->block + (cl_ulong)plan->role_fold_grid * plan->role_lds_slots;
+	return 0;
+}
+
+/* the rest of the plan.  It reads the table's capacity and the groups known: the table stands by now */
+int
+plan_hashed_fold(Device *dev, Program *prog, const preagg_request &req, const hashed_knobs &knobs, hashed_plan *plan)
+{
+	strom_gpupreagg *sess = req.sess;
+	cl_uint		nrows = req.nrows;
+	unsigned	ncus = (unsigned)dev->prop.multiProcessorCount, block = plan->block;
+	int			errcode = 0;
+
+	/* hash roles, the role map and the partition plan scan a COLUMN chunk's arrays as they are: not
+	 * for a program with text / character(n) variables (their column holds offsets that each row
+	 * turns into an address -- strom_kvars_from_column, the one-role walk does it) */
+	plan->column_streams = (req.format == KDS_FORMAT_COLUMN && !(prog->extra_flags & DEVTYPE_IS_VARLENA));
+	/*
+	 * More groups than the hash roles' LDS tables take together (or than a few roles, each a
+	 * scan of the chunk, are worth): the chunk is ordered by hash partition first and folded
+	 * unit by unit (strom_gpupreagg.h: gpupreagg_hash_check_parts ... _fold_parts).  1e8 rows,
+	 * 1e5 / 1e6 groups: 23 / 42 ms through the global table; profiles/r02_hashed_partitions.txt
+	 */
+	/* nothing known about the group count yet (no hint, first chunk; every chunk of the stateless
+	 * per-chunk message): a large chunk takes the plan whose cost does not depend on it -- 2.6 ms
+	 * per 1e8 rows whatever the count, against 0.7 ... 14 ms through the LDS table and the global one */
+	bool		unknown = (sess->groups_known == 0 && nrows >= (4u << 20));
+	plan->use_parts = (nrows > 0 && ((cl_ulong)sess->groups_known >= knobs.parts_min || (unknown && knobs.parts_min > 0)) &&
+					   !knobs.no_parts);
+	if (!plan->use_parts)
+		return 0;
+	plan->fn_pcheck = prog->get_function(dev, "gpupreagg_hash_check_parts", &errcode);
+	plan->fn_plan = plan->fn_pcheck ? prog->get_function(dev, "gpupreagg_hash_part_plan", &errcode) : nullptr;
+	hipFunction_t fn_scatter = plan->fn_plan ? prog->get_function(dev, "gpupreagg_hash_scatter", &errcode) : nullptr;
+	hipFunction_t fn_scatter_lds = fn_scatter ? prog->get_function(dev, "gpupreagg_hash_scatter_lds", &errcode) : nullptr;
+	plan->fn_units = fn_scatter_lds ? prog->get_function(dev, "gpupreagg_hash_fold_parts", &errcode) : nullptr;
+	if (!plan->fn_units)
+		return errcode;
+	/* the units' LDS table: no role queues, one work-group per CU unless two tables fit */
+	plan->unit_lds_slots = hash_lds_slots(sess, knobs, &plan->unit_lds_bytes, true);
+	plan->unit_fold_grid = ncus * (plan->unit_lds_bytes <= 79 * 1024 ? 2 : 1);
+	/*
+	 * its size in threads is the CU's whole occupancy, so the full GPUPREAGG_BLOCK (1024: four waves
+	 * per SIMD).  Smaller work-groups are slower all the way: 256 / 512 / 1024 threads fold 1e8 rows
+	 * at 1e6 groups in 7.0 / 4.1 / 3.2 ms, and the LDS scatter likewise (profiles/r03_hashed_block_sweep.txt).
+	 */
+	plan->unit_fold_block = (knobs.fold_block && knobs.fold_block <= block ? knobs.fold_block : block);
+	/*
+	 * partitions: as few as keep a partition's groups within 5/8 of a unit's LDS table --
+	 * the fewer, the longer the runs the scatter writes (a tile of ~4096 rows leaves in
+	 * runs of 4096 / nparts records)
+	 */
+	cl_uint		nparts = 256;
+	cl_ulong	per_unit = (cl_ulong)plan->unit_lds_slots * 5 / 8;
+	while (nparts < 4096 && (cl_ulong)sess->groups_known > (cl_ulong)nparts * per_unit)
+		nparts <<= 1;
+	if (knobs.parts)
+		nparts = knobs.parts;
+	/* a unit is a whole partition unless the partition is four times the average (one
+	 * heavy key must not be one work-group's job): every unit ends in a flush of its
+	 * groups to the global table, the fewer the better */
+	cl_uint		unit_rows = std::max<cl_uint>(32768, (cl_uint)std::min<cl_ulong>(1u << 30, 4 * (cl_ulong)nrows / nparts));
+	if (knobs.unit_rows)
+		unit_rows = knobs.unit_rows;
+	int			log2cap = bits_for(sess->hash_capacity) - 1, log2parts = bits_for(nparts) - 1;
+	size_t		nvals = 0;
+	for (int resno : sess->agg_resno)
+		nvals += (sess->targets[resno].kind != STROM_PREAGG_NROWS ? 1 : 0);
+	size_t		reclen = plan->reclen = 8 * (1 + sess->key_resno.size() + nvals);
+	plan->nparts = nparts;
+	plan->max_units = nparts + nrows / unit_rows + 1;
+	plan->ctl_img = { nparts, (cl_uint)(log2cap > log2parts ? log2cap - log2parts : 0), unit_rows, 0, 0, 0, plan->max_units, (cl_uint)reclen };
+	plan->check_block = knobs.check_block;
+	plan->check_grid = std::max(1u, std::min<unsigned>((nrows + 2 * knobs.check_block - 1) / (2 * knobs.check_block),
+													   ncus * knobs.check_per_cu));
+	/* the scatter goes through LDS (records leave in runs) when a tile of at least one row
+	 * per thread fits next to the partitions' counters */
+	size_t		stage_fixed = 12 * (size_t)nparts + 128, stage_budget = 159 * 1024;
+	unsigned	sblock = (knobs.scatter_block && knobs.scatter_block <= block ? knobs.scatter_block : block);
+	if (nparts <= 4 * sblock && stage_fixed < stage_budget && !knobs.no_lds_scatter)
+		plan->lds_rows = (cl_uint)std::min<size_t>(4, (stage_budget - stage_fixed) / ((reclen + 2) * sblock));
+	if (knobs.scatter_rows)
+		plan->lds_rows = std::min(plan->lds_rows, knobs.scatter_rows);
+	bool		lds = (plan->lds_rows > 0);
+	size_t		tile = (lds ? (size_t)sblock * plan->lds_rows : (size_t)block * 32);
+	plan->fn_scatter = (lds ? fn_scatter_lds : fn_scatter);
+	plan->scatter_block = (lds ? sblock : block);
+	plan->scatter_lds_bytes = (lds ? stage_fixed + tile * (reclen + 2) : 0);
+	plan->scatter_grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nrows + tile - 1) / tile,
+																		 (size_t)ncus * (plan->scatter_lds_bytes <= 72 * 1024 ? 2 : 1)));
+	return 0;
+}
+
+/* the table a fold needs: made, or grown when a merge / import made it before the first fold
+ * (at the session's initial size): 'min_capacity' slots whatever made the table */
+int
+hash_table_for_fold(strom_gpupreagg *sess, cl_ulong min_capacity)
+{
+	if (sess->htab)
+		return ((cl_ulong)sess->hash_capacity < min_capacity ? hash_table_grow(sess, min_capacity) : 0);
+	cl_ulong	capacity = sess->hash_capacity;
+	while (capacity < min_capacity)
+		capacity <<= 1;
+	sess->hash_capacity = (cl_uint)capacity;
+	return hash_table_new(sess, sess->hash_capacity, &sess->htab, &sess->htab_bytes, nullptr);
+}
+
+/*
+ * the turns of a fold over 'nrows' rows, both plans: make room for the groups the turn may bring, launch,
+ * and when rows (roles) or units (partition plan) were deferred for want of room, wait and go round with
+ * them.  While even 'incoming' new groups fit under the fill limit nothing can be deferred and the task
+ * stays asynchronous.  launch(turn, carried, claim_limit, a_turn, p_count) queues one turn: 'carried' is
+ * what the turn before deferred (0 in turn 0); with p_count it resets the device's count of deferred rows /
+ * units before the kernel and says in *p_count where it is: the loop reads it back behind the fold.
+ *
+ * a_turn is the fold's turn for gpupreagg_hash_sum_account: the parity; 'attempt' is 4 on a second
+ * attempt whose failed proof is final; relaunches for deferred work add 2.  The parity advances
+ * here, where a fold's first launch is queued, and nowhere else: that launch always writes the slot
+ * the next fold reads (gpupreagg_hash_sum_account, or gpupreagg_hash_sum_carry when it folds
+ * nothing).  A request that queues no fold -- no rows, a failure on the way -- leaves the slots
+ * alone and so must leave the parity alone.
+ */
+template <typename Launch>
+bool
+hash_fold_turns(strom_task_impl *task, strom_gpupreagg *sess, cl_ulong headroom, cl_uint nrows,
+				bool deferred_are_rows, cl_uint attempt, Launch launch)
+{
+	cl_uint		sum_turn = (sess->sum_turn & 1u) | attempt, incoming = nrows, carried = 0;
+
+	for (int turn = 0; incoming > 0; turn++)
+	{
+		cl_ulong	fill_limit = hash_fill_limit(sess, headroom);
+		if (sess->groups_upper + incoming > fill_limit)
+		{
+			/* the bound is stale or the table is small: look */
+			cl_uint	ngroups = 0;
+			int		rc = hash_table_ngroups(sess, &ngroups, nullptr);
+			if (rc == 0)
+			{
+				sess->groups_upper = ngroups;
+				/* (geometric: what was deferred says little about the groups in it) */
+				if (turn > 0 || (cl_ulong)ngroups * 2 > fill_limit)
+					rc = hash_table_grow(sess, (cl_ulong)sess->hash_capacity * 4);
+			}
+			if (rc)
+			{
+				task_fail(task, rc);
+				return false;
+			}
+			fill_limit = hash_fill_limit(sess, headroom);
+		}
+		bool		may_defer = (sess->groups_upper + incoming > fill_limit);
+		cl_uint		claim_limit = (may_defer ? (cl_uint)fill_limit : ~0u), deferred = 0;
+		const void *d_count = nullptr;
+		if (!launch(turn, carried, claim_limit, sum_turn | (turn > 0 ? 2u : 0u), may_defer ? &d_count : nullptr))
+			return false;
+		task->pfm.num_kern_exec++;
+		if (turn == 0)
+			sess->sum_turn++;
+		if (!may_defer)
+		{
+			sess->groups_upper += incoming;
+			break;
+		}
+		REQ_CHECK_OR(hipMemcpyAsync(&deferred, d_count, sizeof(cl_uint), hipMemcpyDeviceToHost, task->stream),
+					 "recv the deferred count", false);
+		REQ_CHECK_OR(hipStreamSynchronize(task->stream), "hashed fold's turn", false);
+		sess->groups_upper = std::min<cl_ulong>(sess->groups_upper + incoming, sess->hash_capacity);
+		if (deferred == 0)
+			break;
+		carried = deferred;
+		if (deferred_are_rows)
+			incoming = deferred;		/* (units: any of the chunk's rows may still bring a group) */
+	}
+	return true;
+}
+
+/* what every kernel over the chunk begins with: kern_gpupreagg, chunk, toast (none), row map */
+struct chunk_args { void *kg; const void *kds, *toast, *map; };
+
+/* launch step D, partition plan -- check, plan, scatter, then the fold, unit by unit.  A unit with a new
+ * group beyond the claim limit comes back on the redo list with nothing merged: the table grows and the
+ * list is run.  False: the task has failed. */
+bool
+queue_partition_plan(strom_task_impl *task, const preagg_request &req, const hashed_plan &plan,
+					 const sent_request &sent, cl_uint attempt)
+{
+	strom_gpupreagg *sess = req.sess;
+	Device	   *dev = task->dev;
+	cl_uint		nrows = req.nrows, nparts = plan.nparts, max_units = plan.max_units;
+	/* ctl | hist[P] | cursor[P] | units[2 * max_units] | two redo lists of max_units */
+	size_t		ctl_len = sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)4 * max_units);
+	char	   *d_ctl = (char *)dev->pool.alloc(ctl_len);
+	char	   *d_partmap = (char *)dev->pool.alloc(STROMALIGN((size_t)nrows * sizeof(cl_ushort)));
+	char	   *d_records = (char *)dev->pool.alloc((size_t)nrows * plan.reclen);
+	for (char *p : { d_ctl, d_partmap, d_records })
+		if (p) task->devbufs.push_back(p);
+	if (!d_ctl || !d_partmap || !d_records || sent.kg_len + 128 + sizeof(gpupreagg_part_ctl) > PinnedPool::BLOCK)
+	{
+		task_fail(task, StromError_OutOfMemory);
+		return false;
+	}
+	char	   *stage_ctl = sent.stage + sent.kg_len + 64;
+	memcpy(stage_ctl, &plan.ctl_img, sizeof(plan.ctl_img));
+	REQ_CHECK_OR(hipMemsetAsync(d_ctl, 0, sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * nparts, task->stream),
+				 "reset partition counts", false);
+	REQ_CHECK_OR(hipMemcpyAsync(d_ctl, stage_ctl, sizeof(gpupreagg_part_ctl), hipMemcpyHostToDevice, task->stream),
+				 "send partition plan", false);
+	chunk_args	ca = { sent.d_kg, sent.d_kds, nullptr, sent.d_rowmap };
+	cl_uint	   *d_words = (cl_uint *)(d_ctl + sizeof(gpupreagg_part_ctl));
+	void	   *a_ctl = d_ctl, *a_hist = d_words, *a_cursor = d_words + nparts, *a_units = d_words + (size_t)2 * nparts;
+	cl_uint	   *d_lists = d_words + (size_t)2 * nparts + (size_t)2 * max_units;
+	void	   *a_partmap = d_partmap, *a_records = d_records;
+	cl_uint		lds_rows = plan.lds_rows, unit_lds_slots = plan.unit_lds_slots;
+	void	   *args_check[] = { &ca.kg, &ca.kds, &ca.toast, &ca.map, &a_partmap, &a_hist, &a_ctl };
+	void	   *args_plan[] = { &a_hist, &a_cursor, &a_units, &a_ctl };
+	/* (the LDS scatter's last parameter is its rows per thread; the direct one ends before it) */
+	void	   *args_scatter[] = { &ca.kg, &ca.kds, &ca.toast, &ca.map, &a_partmap, &a_cursor, &a_records, &a_ctl, &lds_rows };
+	REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_pcheck, plan.check_grid, 1, 1, plan.check_block, 1, 1, 0, task->stream, args_check, nullptr),
+				 "launch gpupreagg hash check (partitions)", false);
+	REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_plan, 1, 1, 1, 256, 1, 1, 0, task->stream, args_plan, nullptr),
+				 "launch gpupreagg partition plan", false);
+	REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_scatter, plan.scatter_grid, 1, 1, plan.scatter_block, 1, 1,
+									   (unsigned)plan.scatter_lds_bytes, task->stream, args_scatter, nullptr),
+				 plan.lds_rows ? "launch gpupreagg hash scatter (LDS)" : "launch gpupreagg hash scatter", false);
+	task->pfm.num_kern_exec += 3;
+	task->pfm.num_kern_prep++;				/* (reported: this request took the partition plan) */
+	return hash_fold_turns(task, sess, plan.headroom, nrows, false, attempt,
+		[&](int turn, cl_uint ntodo, cl_uint claim_limit, cl_uint a_turn, const void **p_count) -> bool
+		{
+			void	   *a_tab = sess->htab, *a_deferred = d_ctl + offsetof(gpupreagg_part_ctl, deferred);
+			/* two redo lists: this turn runs the one the turn before wrote */
+			void	   *a_todo = (turn > 0 ? d_lists + (size_t)max_units * ((turn - 1) & 1) : nullptr);
+			void	   *a_redo = d_lists + (size_t)max_units * (turn & 1);
+			void	   *args[] = { &ca.kg, &a_tab, &claim_limit, &a_ctl, &a_units, &a_records, &unit_lds_slots,
+								   &a_todo, &ntodo, &a_redo, &a_turn };
+			if (p_count)
+			{
+				*p_count = a_deferred;
+				REQ_CHECK_OR(hipMemsetAsync(a_deferred, 0, sizeof(cl_uint), task->stream), "reset the redo list", false);
+			}
+			REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_units, plan.unit_fold_grid, 1, 1, plan.unit_fold_block, 1, 1,
+											   (unsigned)plan.unit_lds_bytes, task->stream, args, nullptr),
+						 "launch gpupreagg hash fold (partitions)", false);
+			return true;
+		});
+}
+
+/*
+ * roles: as many as it takes for a role's share of the groups seen so far to fill 5/8 of its LDS
+ * table (64 probes find room at that fill).  Every role scans every row's key columns: ~0.2 ms
+ * per 1e8 rows and role against 23-47 ms through the global table, so up to 64 roles pay
+ * (measured, 1e8 rows: 1000 groups 11.5 -> 1.6 ms with 2 roles, 1e4 groups 26.7 -> 5.1 ms with
+ * 16, 3e4 groups 13.2 ms with 64).  Counted anew in every turn: making room may have looked at
+ * the table and learnt of more groups.
+ */
+cl_uint
+hash_role_count(const strom_gpupreagg *sess, const hashed_knobs &knobs, const hashed_plan &plan)
+{
+	cl_uint		nroles = 1;
+	cl_ulong	per_role = std::max<cl_ulong>(1, (cl_ulong)plan.role_lds_slots * knobs.fill_num / knobs.fill_den);
+	cl_ulong	known = sess->groups_known;
+	if (plan.column_streams && known > per_role && known <= per_role * 64)
+		while (nroles < 64 && (cl_ulong)nroles * per_role < known)
+			nroles <<= 1;
+	if (plan.column_streams && knobs.roles)
+		nroles = knobs.roles;
+	return nroles;
+}
+
+/* launch step D, hash roles -- pass 1, errors only (a chunk with a CpuReCheck row is not folded at all),
+ * then the fold.  Rows that need a new group beyond the claim limit come back as a row map, the table
+ * grows, and they are folded again.  False: the task has failed. */
+bool
+queue_role_fold(strom_task_impl *task, const preagg_request &req, const hashed_knobs &knobs,
+				const hashed_plan &plan, const sent_request &sent, cl_uint attempt)
+{
+	strom_gpupreagg *sess = req.sess;
+	Device	   *dev = task->dev;
+	chunk_args	ca = { sent.d_kg, sent.d_kds, nullptr, sent.d_rowmap };
+	cl_uint		nrows = req.nrows, lds_slots = plan.role_lds_slots;
+	unsigned	block = plan.block;
+	/*
+	 * role map: when the fold will run with hash roles (COLUMN chunk, no row map, more
+	 * groups than one LDS table takes) the check pass leaves one byte per row -- the
+	 * row's role -- and the roles' scans read that instead of the qual's and the keys'
+	 * columns.  Padded with ROLE_NONE to whole scan tiles (16 rows per lane of a
+	 * fold work-group).
+	 */
+	void	   *a_rolemap = nullptr;
+	if (plan.column_streams && !ca.map && nrows > 0 &&
+		(cl_ulong)sess->groups_known > (cl_ulong)lds_slots * 5 / 8 && !knobs.no_rolemap)
+	{
+		size_t	tile = (size_t)block * 16;
+		size_t	len = (((size_t)nrows + tile - 1) / tile) * tile;
+		a_rolemap = dev->pool.alloc(len);
+		if (a_rolemap)
+		{
+			task->devbufs.push_back(a_rolemap);
+			REQ_CHECK_OR(hipMemsetAsync(a_rolemap, 0xff, len, task->stream), "pad the role map", false);
+		}
+	}
+	{
+		void	   *a_tab = sess->htab, *a_nodefer = nullptr;
+		cl_uint		no_limit = ~0u, one_role = 1;
+		void	   *args[] = { &ca.kg, &ca.kds, &ca.toast, &ca.map, &a_tab, &no_limit, &a_nodefer, &lds_slots,
+							   &one_role, &a_rolemap };
+		/* (the kernels deal tiles to 8 XCDs: grids are multiples of 8) */
+		unsigned	maxgrid = (unsigned)dev->prop.multiProcessorCount * 8;
+		unsigned	grid = std::max(8u, std::min<unsigned>((nrows + 255) / 256 + 7, maxgrid) & ~7u);
+		REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_check, grid, 1, 1, 256, 1, 1, 0, task->stream, args, nullptr),
+					 "launch gpupreagg hash check", false);
+		task->pfm.num_kern_exec++;
+	}
+	void	   *d_defer[2] = { nullptr, nullptr };
+	return hash_fold_turns(task, sess, plan.headroom, nrows, true, attempt,
+		[&](int turn, cl_uint carried, cl_uint claim_limit, cl_uint a_turn, const void **p_count) -> bool
+		{
+			cl_uint		todo = (turn > 0 ? carried : nrows);
+			void	   *a_tab = sess->htab;
+			/* (the rows a turn deferred are the next launch's row map: the scan over the columns) */
+			const void *a_map = (turn > 0 ? d_defer[(turn - 1) & 1] : ca.map);
+			void	   *a_defer = nullptr;
+			if (p_count)
+			{
+				if (!d_defer[turn & 1])
+				{
+					d_defer[turn & 1] = dev->pool.alloc(offsetof(kern_row_map, rindex) + sizeof(cl_int) * (size_t)todo);
+					if (!d_defer[turn & 1])
+					{
+						task_fail(task, StromError_OutOfMemory);
+						return false;
+					}
+					task->devbufs.push_back(d_defer[turn & 1]);
+				}
+				*p_count = a_defer = d_defer[turn & 1];		/* (a kern_row_map begins with its count) */
+				REQ_CHECK_OR(hipMemsetAsync(a_defer, 0, offsetof(kern_row_map, rindex), task->stream),
+							 "reset deferred rows", false);
+			}
+			cl_uint		nroles = hash_role_count(sess, knobs, plan);
+			void	   *a_rm = (turn == 0 && nroles > 1 ? a_rolemap : nullptr);
+			void	   *args[] = { &ca.kg, &ca.kds, &ca.toast, &a_map, &a_tab, &claim_limit, &a_defer, &lds_slots,
+								   &nroles, &a_rm, &a_turn };
+			unsigned	unit = 8 * nroles;
+			unsigned	grid = std::min<unsigned>(((todo + block - 1) / block + unit - 1) / unit * unit, plan.role_fold_grid);
+			grid = std::max(unit, grid / unit * unit);
+			REQ_CHECK_OR(hipModuleLaunchKernel(plan.fn_fold, grid, 1, 1, block, 1, 1, (unsigned)plan.role_lds_bytes,
+											   task->stream, args, nullptr),
+						 "launch gpupreagg hash fold", false);
+			return true;
+		});
+}
+
+/* The hashed launch, step by step.  sess->lock is held throughout, the turns that wait for the device
+ * included: the table, its bounds and the sums' parity belong to one fold at a time. */
 void
 gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 {
 	strom_gpupreagg *sess = req.sess;
 	Device	   *dev = task->dev;
 	Program	   *prog = sess->prog;
-	int			errcode = 0;
 	std::lock_guard<std::mutex> g(sess->lock);
 
 	(void)hipSetDevice(dev->hip_id);
@@ -1676,471 +2102,45 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 	}
 	task->pfm.time_kern_build = (cl_ulong)prog->build_usec;
 	task->stream = dev->streams[0];
-	hipFunction_t fn_check = prog->get_function(dev, "gpupreagg_hash_check", &errcode);
-	hipFunction_t fn_fold = fn_check ? prog->get_function(dev, "gpupreagg_hash_fold", &errcode) : nullptr;
-	if (!fn_check || !fn_fold)
+	const hashed_knobs knobs = read_hashed_knobs();							/* A */
+	/* B, around the table: the roles' geometry says how large it must be, the rest reads it */
+	hashed_plan	plan;
+	int			rc = plan_role_table(dev, prog, sess, knobs, &plan);
+	if (rc == 0)
+		rc = hash_table_for_fold(sess, 4 * plan.headroom);
+	if (rc == 0)
+		rc = plan_hashed_fold(dev, prog, req, knobs, &plan);
+	/* a second attempt: the sums' bound is measured from the table first */
+	if (rc == 0 && second)
+		rc = hash_sum_refresh(sess);
+	if (rc)
 	{
-		task_fail(task, errcode);
+		task_fail(task, rc);
 		return;
 	}
-	/* hash roles, the role map and the partition plan scan a COLUMN chunk's arrays as they are: not
-	 * for a program with text / character(n) variables (their column holds offsets that each row
-	 * turns into an address -- strom_kvars_from_column, the one-role walk does it) */
-	const bool	column_streams = (req.format == KDS_FORMAT_COLUMN && !(prog->extra_flags & DEVTYPE_IS_VARLENA));
-	/*
-	 * geometry: two work-groups per CU (64 KB of LDS each).  Slots can be
-	 * claimed past the fill limit by threads that raced through the limit test
-	 * (one each at most) and by the work-groups' final LDS flushes: that much
-	 * headroom, and an eighth of the table on top, always stays free.
-	 */
-	size_t		lds_bytes = 0;
-	cl_uint		lds_slots = hash_lds_slots(sess, &lds_bytes);
-	unsigned	block = (unsigned)sess->block;
-	unsigned	fold_grid = (unsigned)dev->prop.multiProcessorCount * (lds_bytes <= 72 * 1024 ? 2 : 1);
-	cl_ulong	headroom = (cl_ulong)fold_grid * block + (cl_ulong)fold_grid * lds_slots;
-	if (!sess->htab)
-	{
-		cl_ulong	capacity = sess->hash_capacity;
-		while (capacity < 4 * headroom)
-			capacity <<= 1;
-		sess->hash_capacity = (cl_uint)capacity;
-		int rc = hash_table_new(sess, sess->hash_capacity, &sess->htab, &sess->htab_bytes, nullptr);
-		if (rc)
-		{
-			task_fail(task, rc);
-			return;
-		}
-	}
-	else if ((cl_ulong)sess->hash_capacity < 4 * headroom)
-	{
-		/* a table made by a merge / import before the first fold (at the session's initial
-		 * size): a fold needs its headroom of free slots whatever made the table */
-		int rc = hash_table_grow(sess, 4 * headroom);
-		if (rc)
-		{
-			task_fail(task, rc);
-			return;
-		}
-	}
-	/* the fold's turn (gpupreagg_hash_sum_account): parity; 4 = second attempt, after the
-	 * bound was measured; relaunches for deferred rows add 2 */
-	/* (bit 2 -- "a failed proof is final: CpuReCheck" -- is no longer asked for: the host sends an
-	 * unproven chunk to the exact fold instead, gpupreagg_hashed_exact) */
-	/* the parity advances where a fold's first launch is queued, below, and nowhere else: that
-	 * launch always writes the slot the next fold reads (gpupreagg_hash_sum_account, or
-	 * gpupreagg_hash_sum_carry when it folds nothing).  A request that queues no fold -- no rows,
-	 * a failure on the way -- leaves the slots alone and so must leave the parity alone */
-	cl_uint		sum_turn = (sess->sum_turn & 1u) | ((second && getenv("STROM_GPUPREAGG_HASH_NO_EXACT")) ? 4u : 0u);
-	if (second)
-	{
-		int rc = hash_sum_refresh(sess);
-		if (rc)
-		{
-			task_fail(task, rc);
-			return;
-		}
-	}
-	/* integer sums never wrap (strom_gpupreagg.h): rows of the request, what is known about
+	/* C.  integer sums never wrap (strom_gpupreagg.h): rows of the request, what is known about
 	 * the inputs before the check pass measures the rest */
 	sent_request sent;
 	if (!send_request(task, req, task->stream, sess->static_magbits, 0, false, nullptr, &sent))	/* ev[0] */
 		return;
-	char	   *stage = sent.stage, *d_kg = sent.d_kg;
-	const size_t kg_len = sent.kg_len;
-	const void *d_kds = sent.d_kds, *d_rowmap = sent.d_rowmap;
 	task_event(task);									/* ev[1] */
-	/*
-	 * More groups than the hash roles' LDS tables take together (or than a few roles, each a
-	 * scan of the chunk, are worth): the chunk is ordered by hash partition first and folded
-	 * unit by unit (strom_gpupreagg.h: gpupreagg_hash_check_parts ... _fold_parts).  1e8 rows,
-	 * 1e5 / 1e6 groups: 23 / 42 ms through the global table; profiles/r02_hashed_partitions.txt
-	 */
-	cl_ulong	parts_min = 10000;
-	if (const char *v = getenv("STROM_GPUPREAGG_HASH_PARTS_MIN"))
-		parts_min = strtoul(v, nullptr, 10);
-	/* nothing known about the group count yet (no hint, first chunk; every chunk of the stateless
-	 * per-chunk message): a large chunk takes the plan whose cost does not depend on it -- 2.6 ms
-	 * per 1e8 rows whatever the count, against 0.7 ... 14 ms through the LDS table and the global one */
-	bool		unknown = (sess->groups_known == 0 && req.nrows >= (4u << 20));
-	bool		use_parts = (req.nrows > 0 && ((cl_ulong)sess->groups_known >= parts_min || (unknown && parts_min > 0)) &&
-							 !getenv("STROM_GPUPREAGG_HASH_NO_PARTS"));
-	if (use_parts)
-	{
-		hipFunction_t fn_pcheck = prog->get_function(dev, "gpupreagg_hash_check_parts", &errcode);
-		hipFunction_t fn_plan = fn_pcheck ? prog->get_function(dev, "gpupreagg_hash_part_plan", &errcode) : nullptr;
-		hipFunction_t fn_scatter = fn_plan ? prog->get_function(dev, "gpupreagg_hash_scatter", &errcode) : nullptr;
-		hipFunction_t fn_scatter_lds = fn_scatter ? prog->get_function(dev, "gpupreagg_hash_scatter_lds", &errcode) : nullptr;
-		hipFunction_t fn_units = fn_scatter_lds ? prog->get_function(dev, "gpupreagg_hash_fold_parts", &errcode) : nullptr;
-		if (!fn_units)
-		{
-			task_fail(task, errcode);
-			return;
-		}
-		cl_uint		nrows = req.nrows;
-		/*
-		 * partitions: as few as keep a partition's groups within 5/8 of a unit's LDS table --
-		 * the fewer, the longer the runs the scatter writes (a tile of ~4096 rows leaves in
-		 * runs of 4096 / nparts records)
-		 */
-		cl_uint		nparts = 256;
-		{
-			size_t	b;
-			cl_ulong per_unit = (cl_ulong)hash_lds_slots(sess, &b, true) * 5 / 8;
-			while (nparts < 4096 && (cl_ulong)sess->groups_known > (cl_ulong)nparts * per_unit)
-				nparts <<= 1;
-		}
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_PARTS"))
-		{
-			int want = atoi(v);
-			if (want >= 64 && want <= 4096 && (want & (want - 1)) == 0)
-				nparts = (cl_uint)want;
-		}
-		/* a unit is a whole partition unless the partition is four times the average (one
-		 * heavy key must not be one work-group's job): every unit ends in a flush of its
-		 * groups to the global table, the fewer the better */
-		cl_uint		unit_rows = std::max<cl_uint>(32768, (cl_uint)std::min<cl_ulong>(1u << 30, 4 * (cl_ulong)nrows / nparts));
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_UNIT_ROWS"))
-			unit_rows = std::max(1024, atoi(v));
-		cl_uint		log2cap = 0, log2parts = 0;
-		while ((1UL << (log2cap + 1)) <= sess->hash_capacity)
-			log2cap++;
-		while ((1u << (log2parts + 1)) <= nparts)
-			log2parts++;
-		size_t		nvals = 0;
-		for (int resno : sess->agg_resno)
-			nvals += (sess->targets[resno].kind != STROM_PREAGG_NROWS ? 1 : 0);
-		size_t		reclen = 8 * (1 + sess->key_resno.size() + nvals);
-		cl_uint		max_units = nparts + nrows / unit_rows + 1;
-		gpupreagg_part_ctl ctl_img = { nparts, (log2cap > log2parts ? log2cap - log2parts : 0), unit_rows, 0, 0, 0, max_units, (cl_uint)reclen };
-		/* ctl | hist[P] | cursor[P] | units[2 * max_units] | two redo lists of max_units */
-		size_t		ctl_len = sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)4 * max_units);
-		char	   *d_ctl = (char *)dev->pool.alloc(ctl_len);
-		char	   *d_partmap = (char *)dev->pool.alloc(STROMALIGN((size_t)nrows * sizeof(cl_ushort)));
-		char	   *d_records = (char *)dev->pool.alloc((size_t)nrows * reclen);
-		if (d_ctl) task->devbufs.push_back(d_ctl);
-		if (d_partmap) task->devbufs.push_back(d_partmap);
-		if (d_records) task->devbufs.push_back(d_records);
-		if (!d_ctl || !d_partmap || !d_records || kg_len + 128 + sizeof(gpupreagg_part_ctl) > PinnedPool::BLOCK)
-		{
-			task_fail(task, StromError_OutOfMemory);
-			return;
-		}
-		char	   *stage_ctl = stage + kg_len + 64;
-		memcpy(stage_ctl, &ctl_img, sizeof(ctl_img));
-		REQ_CHECK(hipMemsetAsync(d_ctl, 0, sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * nparts, task->stream),
-				  "reset partition counts");
-		REQ_CHECK(hipMemcpyAsync(d_ctl, stage_ctl, sizeof(gpupreagg_part_ctl), hipMemcpyHostToDevice, task->stream),
-				  "send partition plan");
-		void	   *a_kg = d_kg;
-		const void *a_kds = d_kds;
-		const void *a_toast = nullptr;
-		const void *a_map = d_rowmap;
-		void	   *a_ctl = d_ctl;
-		void	   *a_hist = d_ctl + sizeof(gpupreagg_part_ctl);
-		void	   *a_cursor = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * nparts;
-		void	   *a_units = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * 2 * nparts;
-		void	   *a_partmap = d_partmap;
-		void	   *a_records = d_records;
-		unsigned	ncus = (unsigned)dev->prop.multiProcessorCount;
-		{
-			void	   *args[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_partmap, &a_hist, &a_ctl };
-			/* (1024 threads, two work-groups per CU: 2.37 against 2.48 ms for the whole plan with 256 x 4,
-			 * the other combinations in between -- scripts/hashed_check_sweep.sh) */
-			unsigned	cblock = 1024, cper = 2;
-			if (const char *v = getenv("STROM_GPUPREAGG_HASH_CHECK_BLOCK"))
-			{
-				int want = atoi(v);
-				if (want == 256 || want == 512 || want == 1024)
-					cblock = (unsigned)want;
-			}
-			if (const char *v = getenv("STROM_GPUPREAGG_HASH_CHECK_PER_CU"))
-				cper = (unsigned)std::max(1, atoi(v));
-			unsigned	grid = std::max(1u, std::min<unsigned>((nrows + 2 * cblock - 1) / (2 * cblock), ncus * cper));
-			REQ_CHECK(hipModuleLaunchKernel(fn_pcheck, grid, 1, 1, cblock, 1, 1, 0, task->stream, args, nullptr),
-					  "launch gpupreagg hash check (partitions)");
-		}
-		{
-			void	   *args[] = { &a_hist, &a_cursor, &a_units, &a_ctl };
-			REQ_CHECK(hipModuleLaunchKernel(fn_plan, 1, 1, 1, 256, 1, 1, 0, task->stream, args, nullptr),
-					  "launch gpupreagg partition plan");
-		}
-		/* the scatter goes through LDS (records leave in runs) when a tile of at least one row
-		 * per thread fits next to the partitions' counters */
-		size_t		stage_fixed = 12 * (size_t)nparts + 128;
-		size_t		stage_budget = 159 * 1024;
-		cl_uint		lds_rows = 0;
-		unsigned	sblock = block;
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_SCATTER_BLOCK"))
-		{
-			int want = atoi(v);
-			if ((want == 256 || want == 512 || want == 1024) && (unsigned)want <= block)
-				sblock = (unsigned)want;
-		}
-		if (nparts <= 4 * sblock && stage_fixed < stage_budget && !getenv("STROM_GPUPREAGG_HASH_NO_LDS_SCATTER"))
-			lds_rows = (cl_uint)std::min<size_t>(4, (stage_budget - stage_fixed) / ((reclen + 2) * sblock));
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_SCATTER_ROWS"))
-			lds_rows = std::min<cl_uint>(lds_rows, (cl_uint)std::max(1, atoi(v)));
-		if (lds_rows > 0)
-		{
-			size_t		stage_bytes = stage_fixed + (size_t)lds_rows * sblock * (reclen + 2);
-			void	   *args[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_partmap, &a_cursor, &a_records, &a_ctl, &lds_rows };
-			size_t		tile = (size_t)sblock * lds_rows;
-			unsigned	grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nrows + tile - 1) / tile,
-																			   (size_t)ncus * (stage_bytes <= 72 * 1024 ? 2 : 1)));
-			REQ_CHECK(hipModuleLaunchKernel(fn_scatter_lds, grid, 1, 1, sblock, 1, 1, (unsigned)stage_bytes,
-											task->stream, args, nullptr),
-					  "launch gpupreagg hash scatter (LDS)");
-		}
-		else
-		{
-			void	   *args[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_partmap, &a_cursor, &a_records, &a_ctl };
-			size_t		tile = (size_t)block * 32;
-			unsigned	grid = (unsigned)std::max<size_t>(1, std::min<size_t>((nrows + tile - 1) / tile, (size_t)ncus * 2));
-			REQ_CHECK(hipModuleLaunchKernel(fn_scatter, grid, 1, 1, block, 1, 1, 0, task->stream, args, nullptr),
-					  "launch gpupreagg hash scatter");
-		}
-		task->pfm.num_kern_exec += 3;
-		task->pfm.num_kern_prep++;				/* (reported: this request took the partition plan) */
-		/*
-		 * fold, unit by unit.  While even nrows new groups fit under the fill limit the
-		 * task stays asynchronous; otherwise a unit with a new group beyond the limit comes
-		 * back on the redo list with nothing merged: the table grows and the list is run.
-		 */
-		size_t		lds_bytes = 0;				/* (the units' table, not the roles') */
-		cl_uint		lds_slots = hash_lds_slots(sess, &lds_bytes, true);
-		unsigned	fold_grid = ncus * (lds_bytes <= 79 * 1024 ? 2 : 1);
-		/*
-		 * the unit's LDS table leaves room for one work-group per CU: its size in threads is the
-		 * CU's whole occupancy, so the full GPUPREAGG_BLOCK (1024: four waves per SIMD).  Smaller
-		 * work-groups are slower all the way: 256 / 512 / 1024 threads fold 1e8 rows at 1e6 groups
-		 * in 7.0 / 4.1 / 3.2 ms, and the LDS scatter likewise (profiles/r03_hashed_block_sweep.txt).
-		 */
-		unsigned	fold_block = block;
-		if (const char *v = getenv("STROM_GPUPREAGG_HASH_FOLD_BLOCK"))
-		{
-			int want = atoi(v);
-			if ((want == 256 || want == 512 || want == 1024) && (unsigned)want <= block)
-				fold_block = (unsigned)want;
-		}
-		char	   *d_lists = d_ctl + sizeof(gpupreagg_part_ctl) + sizeof(cl_uint) * ((size_t)2 * nparts + (size_t)2 * max_units);
-		void	   *a_todo = nullptr;
-		cl_uint		ntodo = 0;
-		for (int turn = 0;; turn++)
-		{
-			cl_ulong	fill_limit = hash_fill_limit(sess, headroom);
-			if (sess->groups_upper + nrows > fill_limit)
-			{
-				cl_uint	ngroups = 0;
-				int		rc = hash_table_ngroups(sess, &ngroups, nullptr);
-				if (rc == 0)
-				{
-					sess->groups_upper = ngroups;
-					if (turn > 0 || (cl_ulong)ngroups * 2 > fill_limit)
-						rc = hash_table_grow(sess, (cl_ulong)sess->hash_capacity * 4);
-				}
-				if (rc)
-				{
-					task_fail(task, rc);
-					return;
-				}
-				fill_limit = hash_fill_limit(sess, headroom);
-			}
-			bool		may_defer = (sess->groups_upper + nrows > fill_limit);
-			cl_uint		claim_limit = (may_defer ? (cl_uint)fill_limit : ~0u);
-			void	   *a_tab = sess->htab;
-			void	   *a_redo = d_lists + sizeof(cl_uint) * (size_t)max_units * (turn & 1);
-			if (may_defer)
-				REQ_CHECK(hipMemsetAsync(d_ctl + offsetof(gpupreagg_part_ctl, deferred), 0, sizeof(cl_uint), task->stream),
-						  "reset the redo list");
-			cl_uint		a_turn = sum_turn | (turn > 0 ? 2u : 0u);
-			void	   *args[] = { &a_kg, &a_tab, &claim_limit, &a_ctl, &a_units, &a_records, &lds_slots,
-								   &a_todo, &ntodo, &a_redo, &a_turn };
-			REQ_CHECK(hipModuleLaunchKernel(fn_units, fold_grid, 1, 1, fold_block, 1, 1, (unsigned)lds_bytes,
-											task->stream, args, nullptr),
-					  "launch gpupreagg hash fold (partitions)");
-			task->pfm.num_kern_exec++;
-			if (turn == 0)
-				sess->sum_turn++;
-			if (!may_defer)
-			{
-				sess->groups_upper += nrows;
-				break;
-			}
-			cl_uint		nredo = 0;
-			REQ_CHECK(hipMemcpyAsync(&nredo, d_ctl + offsetof(gpupreagg_part_ctl, deferred), sizeof(cl_uint),
-									 hipMemcpyDeviceToHost, task->stream),
-					  "recv redo list");
-			REQ_CHECK(hipStreamSynchronize(task->stream), "fold (partitions)");
-			sess->groups_upper = std::min<cl_ulong>(sess->groups_upper + nrows, sess->hash_capacity);
-			if (nredo == 0)
-				break;
-			a_todo = a_redo;
-			ntodo = nredo;
-		}
-	}
-	else
-	{
-		void	   *a_kg = d_kg;
-		const void *a_kds = d_kds;
-		const void *a_toast = nullptr;
-		const void *a_map = d_rowmap;
-		cl_uint		nrows = req.nrows;
-		unsigned	maxgrid = (unsigned)dev->prop.multiProcessorCount * 8;
-		cl_uint		no_limit = ~0u;
-		void	   *a_nodefer = nullptr;
-		/*
-		 * role map: when the fold will run with hash roles (COLUMN chunk, no row map, more
-		 * groups than one LDS table takes) the check pass leaves one byte per row -- the
-		 * row's role -- and the roles' scans read that instead of the qual's and the keys'
-		 * columns.  Padded with ROLE_NONE to whole scan tiles (16 rows per lane of a
-		 * fold work-group).
-		 */
-		void	   *a_rolemap = nullptr;
-		{
-			cl_ulong	per_role0 = (cl_ulong)lds_slots * 5 / 8;
-			if (column_streams && !d_rowmap && nrows > 0 &&
-				(cl_ulong)sess->groups_known > per_role0 && !getenv("STROM_GPUPREAGG_HASH_NO_ROLEMAP"))
-			{
-				size_t	tile = (size_t)block * 16;
-				size_t	len = (((size_t)nrows + tile - 1) / tile) * tile;
-				a_rolemap = dev->pool.alloc(len);
-				if (a_rolemap)
-				{
-					task->devbufs.push_back(a_rolemap);
-					REQ_CHECK(hipMemsetAsync(a_rolemap, 0xff, len, task->stream), "pad the role map");
-				}
-			}
-		}
-		/* pass 1: errors only -- a chunk with a CpuReCheck row is not folded at all */
-		{
-			void	   *a_tab = sess->htab;
-			cl_uint		one_role = 1;
-			void	   *args[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_tab, &no_limit, &a_nodefer, &lds_slots,
-								   &one_role, &a_rolemap };
-			/* (the kernels deal tiles to 8 XCDs: grids are multiples of 8) */
-			unsigned	grid = std::max(8u, std::min<unsigned>((nrows + 255) / 256 + 7, maxgrid) & ~7u);
-			REQ_CHECK(hipModuleLaunchKernel(fn_check, grid, 1, 1, 256, 1, 1, 0, task->stream, args, nullptr),
-					  "launch gpupreagg hash check");
-			task->pfm.num_kern_exec++;
-		}
-		/*
-		 * pass 2: fold.  While even nrows new groups fit under the fill limit
-		 * nothing can be deferred and the task stays asynchronous; otherwise
-		 * rows that need a new group beyond the limit come back as a row map,
-		 * the table grows, and they are folded again.
-		 */
-		cl_uint		todo = nrows;
-		void	   *d_defer[2] = { nullptr, nullptr };
-		int			turn = 0;
-		while (todo > 0)
-		{
-			cl_ulong	fill_limit = hash_fill_limit(sess, headroom);
-			if (sess->groups_upper + todo > fill_limit)
-			{
-				/* the bound is stale or the table is small: look */
-				cl_uint	ngroups = 0;
-				int		rc = hash_table_ngroups(sess, &ngroups, nullptr);
-				if (rc == 0)
-				{
-					sess->groups_upper = ngroups;
-					if (turn > 0 || (cl_ulong)ngroups * 2 > fill_limit)
-						rc = hash_table_grow(sess, (cl_ulong)sess->hash_capacity * 4);	/* geometric: the deferred
-																						 * rows say little about
-																						 * the groups among them */
-				}
-				if (rc)
-				{
-					task_fail(task, rc);
-					return;
-				}
-				fill_limit = hash_fill_limit(sess, headroom);
-			}
-			bool		may_defer = (sess->groups_upper + todo > fill_limit);
-			cl_uint		claim_limit = (may_defer ? (cl_uint)fill_limit : no_limit);
-			void	   *a_tab = sess->htab;
-			void	   *a_defer = nullptr;
-			if (may_defer)
-			{
-				size_t	len = offsetof(kern_row_map, rindex) + sizeof(cl_int) * (size_t)todo;
-				if (!d_defer[turn & 1])
-				{
-					d_defer[turn & 1] = dev->pool.alloc(len);
-					if (!d_defer[turn & 1])
-					{
-						task_fail(task, StromError_OutOfMemory);
-						return;
-					}
-					task->devbufs.push_back(d_defer[turn & 1]);
-				}
-				a_defer = d_defer[turn & 1];
-				REQ_CHECK(hipMemsetAsync(a_defer, 0, offsetof(kern_row_map, rindex), task->stream),
-						  "reset deferred rows");
-			}
-			/*
-			 * roles: as many as it takes for a role's share of the groups seen so
-			 * far to fill 5/8 of its LDS table (64 probes find room at that fill).
-			 * Every role scans every row's key columns: ~0.2 ms per 1e8 rows and
-			 * role against 23-47 ms through the global table, so up to 64 roles
-			 * pay (measured, 1e8 rows: 1000 groups 11.5 -> 1.6 ms with 2 roles, 1e4
-			 * groups 26.7 -> 5.1 ms with 16, 3e4 groups 13.2 ms with 64)
-			 */
-			cl_uint		nroles = 1;
-			cl_ulong	per_role = (cl_ulong)lds_slots * 5 / 8;
-			cl_ulong	known = sess->groups_known;
-			if (const char *v = getenv("STROM_GPUPREAGG_HASH_FILL"))
-				per_role = std::max<cl_ulong>(1, (cl_ulong)lds_slots * (cl_ulong)atoi(v) / 100);
-			if (column_streams && known > per_role && known <= per_role * 64)
-			{
-				while (nroles < 64 && (cl_ulong)nroles * per_role < known)
-					nroles <<= 1;
-			}
-			if (const char *v = getenv("STROM_GPUPREAGG_HASH_ROLES"))
-			{
-				/* 1, 2, 4 ... 64; anything else would break the tile walk */
-				int want = atoi(v);
-				if (column_streams && want >= 1 && want <= 64 && (want & (want - 1)) == 0)
-					nroles = (cl_uint)want;
-			}
-			/* (deferred rows of a later turn are a row map: the scan over the columns) */
-			void	   *a_rm = (turn == 0 && nroles > 1 ? a_rolemap : nullptr);
-			cl_uint		a_turn = sum_turn | (turn > 0 ? 2u : 0u);
-			void	   *args[] = { &a_kg, &a_kds, &a_toast, &a_map, &a_tab, &claim_limit, &a_defer, &lds_slots,
-								   &nroles, &a_rm, &a_turn };
-			unsigned	unit = 8 * nroles;
-			unsigned	grid = std::min<unsigned>(((todo + block - 1) / block + unit - 1) / unit * unit, fold_grid);
-			grid = std::max(unit, grid / unit * unit);
-			REQ_CHECK(hipModuleLaunchKernel(fn_fold, grid, 1, 1, block, 1, 1, (unsigned)lds_bytes,
-											task->stream, args, nullptr),
-					  "launch gpupreagg hash fold");
-			task->pfm.num_kern_exec++;
-			if (turn == 0)
-				sess->sum_turn++;
-			if (!may_defer)
-			{
-				sess->groups_upper += todo;
-				break;
-			}
-			cl_int		ndeferred = 0;
-			REQ_CHECK(hipMemcpyAsync(&ndeferred, a_defer, sizeof(cl_int), hipMemcpyDeviceToHost, task->stream),
-					  "recv deferred rows");
-			REQ_CHECK(hipStreamSynchronize(task->stream), "fold");
-			sess->groups_upper = std::min<cl_ulong>(sess->groups_upper + todo, sess->hash_capacity);
-			todo = (cl_uint)ndeferred;
-			a_map = a_defer;			/* the deferred rows are the next launch's row map */
-			turn++;
-		}
-	}
+	/* D.  (bit 2 of the turn -- "a failed proof is final: CpuReCheck" -- only where the exact fold,
+	 * gpupreagg_hashed_exact, is switched off: the host sends an unproven chunk there instead) */
+	const bool	no_exact = knobs.no_exact;
+	cl_uint		attempt = (second && no_exact ? 4u : 0u);
+	if (!(plan.use_parts ? queue_partition_plan(task, req, plan, sent, attempt)
+						 : queue_role_fold(task, req, knobs, plan, sent, attempt)))
+		return;
 	task_event(task);									/* ev[2] */
-	char   *stage_status = stage + kg_len;
-	REQ_CHECK(hipMemcpyAsync(stage_status, d_kg + offsetof(kern_gpupreagg, status), sizeof(cl_int),
-							 hipMemcpyDeviceToHost, task->stream),
+	char   *stage_status = sent.stage + sent.kg_len;
+	REQ_CHECK(hipMemcpyAsync(stage_status, sent.d_kg + offsetof(kern_gpupreagg, status), sizeof(cl_int), hipMemcpyDeviceToHost, task->stream),
 			  "recv status");
 	REQ_CHECK(hipMemcpyAsync(stage_status + 16, sess->htab, HASH_HEAD_COUNTERS, hipMemcpyDeviceToHost, task->stream),
 			  "recv table head");
 	task->pfm.num_dma_recv += 2;
 	task->pfm.bytes_dma_recv += sizeof(cl_int) + 16;
 	task_event(task);									/* ev[3] */
-	task->finish = [stage_status, sess, req, second](strom_task_impl *t)
+	task->finish = [stage_status, sess, req, second, no_exact](strom_task_impl *t)
 	{
 		cl_int	status;
 		gpupreagg_hash_head head;
@@ -2153,7 +2153,7 @@ gpupreagg_launch_hashed(strom_task_impl *task, preagg_request req, bool second)
 			t->retry = [t, req]() { gpupreagg_launch_hashed(t, req, true); };
 			return;
 		}
-		if (status == StromError_SumRangeUnproven && !req.exact_parent && !getenv("STROM_GPUPREAGG_HASH_NO_EXACT"))
+		if (status == StromError_SumRangeUnproven && !req.exact_parent && !no_exact)
 		{
 			/* rows x largest magnitude still reaches 2^63 -- a bound over ALL groups at once,
 			 * which says little about any one of them: the chunk is folded exactly instead */
